@@ -11,9 +11,15 @@ Default mode ("weak"): a step is one batch of B consecutive synthetic
 per-frame path — ingest, the six detectors, tail, NMS, unary/pairwise costs,
 side<->bottom matching — up to and including the copy of the results into
 host memory in the reference's container layout.  Every rank runs its own
-frames (no collective on the data path).  Rank 0 prints one JSON line.  The
-last batch each context collected inside the timed loop is checked against
-the CPU oracle (`parity_sample`).
+frames (no collective on the data path).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full`
+adds what takes runs of its own: the last batch each context collected inside
+the timed loop is checked against the CPU oracle (`parity_sample`, or
+`video_check` for one video; a mismatch makes the exit status 3) and the CPU
+baselines are measured (`--no-check` / `--no-cpu` leave one of them out).
+`--dump-outputs DIR` writes the results of the last timed step, as the caller
+of the path receives them, to DIR/<name>.npy (see dump_outputs).
 
 `--video-frames N` ("strong", BASELINE config 4): ONE video of N frames split
 into contiguous shards, one per rank (main.cpp:54-82's loop over a shard; a
@@ -89,6 +95,45 @@ def union_ms(iv):
             tot += b - end
             end = b
     return tot
+
+
+DUMP_BUDGET = 60 * 2 ** 20  # bytes of array data --dump-outputs may write (under 64 MB with the .npy headers)
+
+
+def result_arrays(prefix, res):
+    """(name, array) for every array of a result dict (results.KEYS), a
+    structured array as one entry per field."""
+    from locomouse_cpp_amd.results import KEYS
+    out = []
+    for k in KEYS:
+        a = res[k]
+        if a.dtype.names:
+            out.extend((f"{prefix}{k}.{n}", a[n]) for n in a.dtype.names)
+        else:
+            out.append((prefix + k, a))
+    return out
+
+
+def dump_outputs(path, named, budget=DUMP_BUDGET):
+    """--dump-outputs: every (name, array) as path/<name>.npy.  float32 and
+    float64 arrays are written as they are, integer arrays as float64 (exact:
+    every value is below 2**53).  When the arrays together exceed `budget`
+    bytes, each array longer than 4,096 elements is cut to the same fraction
+    of its flattened elements, picked by a generator with a fixed seed (the
+    same elements in every run that produces arrays of the same sizes), in
+    index order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = [(n, np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64))
+            for n, a in named]
+    total = sum(a.nbytes for _, a in arrs)
+    small = sum(a.nbytes for _, a in arrs if a.size <= 4096)
+    frac = 1.0 if total <= budget else max(0.0, (budget - small) / (total - small))
+    rng = np.random.default_rng(0)
+    for n, a in arrs:
+        if frac < 1.0 and a.size > 4096:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def host_cpu_share():
@@ -280,6 +325,9 @@ def run_bb(args):
         ctx.push_device(d.data_ptr() + (i % nbuf) * B * pitch, pitch, B, values=False)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # the per-frame values of the last timed push
+        per = ctx.finish()["frames"][-B:]
+        dump_outputs(args.dump_outputs, [("bb_frames." + n, per[n]) for n in per.dtype.names])
     ctx.close()
     line = {"metric": "whole-video bounding-box pass frames/s (method 0)", "value": args.steps * B / dt,
             "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -287,7 +335,7 @@ def run_bb(args):
             "vs_baseline": None, "dtype": "u8", "data": "synthetic (lm_synth.h scene, resident in HBM)",
             "config": {"workload": workload + "; LocoMouse::computeBoundingBox over the stream", "batch_frames": B,
                        "firstlast_semantics": "integer" if args.bb_semantics else "as executed"}}
-    if not args.no_cpu:
+    if args.cpu:
         from oracle import oracle as O  # CPU baseline only
         nf = 40 if rows <= 256 else 10
         fr = cfg.frames(0, nf)
@@ -407,9 +455,15 @@ def main():
     ap.add_argument("--check-all-ranks", action="store_true",
                     help="every rank compares its sampled batches with the oracle (multi-rank rehearsals)")
     ap.add_argument("--round-robin", action="store_true", help="one host thread drives all streams in turn")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the timed batches against the CPU oracle and measure the "
+                         "CPU baselines (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB: a fixed seeded sample of larger arrays)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the timed batches")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the oracle check of the timed batches")
     ap.add_argument("--workload", choices=["detect", "bb"], default="detect",
                     help="bb: the whole-video bounding-box pass (SURVEY.md §8(f) row 1) instead of the headline path")
     ap.add_argument("--bb-semantics", type=int, default=0, help="firstLastOverT: 0 as executed, 1 integer sums")
@@ -429,6 +483,10 @@ def main():
     resolve_shape(args)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    args.check = args.full and not args.no_check
+    args.cpu = args.full and not args.no_cpu
     if args.workload == "bb":
         return run_bb(args)
     env = rank_env(args)
@@ -684,6 +742,14 @@ def run_stream(args, world, rank, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     gathered = gather_summary(samples, world, rank)
+    if args.dump_outputs:  # each context's last timed batch (the last of a context's samples)
+        last, pos = [], 0
+        for k in range(NS):
+            pos += len(keep[k])
+            last.append(samples[pos - 1][1])
+        pre = f"rank{rank}." if world > 1 else ""
+        dump_outputs(args.dump_outputs, [e for k, res in enumerate(last) for e in result_arrays(f"{pre}ctx{k}.", res)],
+                     DUMP_BUDGET // world)
     total_frames = args.steps * B * NS * world
     fps = total_frames / elapsed
     out = {
@@ -716,7 +782,7 @@ def run_stream(args, world, rank, device):
         "kernel_busy_ms_per_batch": {k: round(union_ms(v) / len(v), 5) for k, v in spans.items()},
         "gathered": gathered,
     }
-    check = not args.no_check and (rank == 0 or args.check_all_ranks)
+    check = args.check and (rank == 0 or args.check_all_ranks)
     if check and f16:
         out["parity_sample"] = {"skipped": "LM_CORR_F16 is the non-parity mode (candidate agreement: "
                                            "tests/test_gpu_f16.py)"}
@@ -740,7 +806,7 @@ def run_stream(args, world, rank, device):
         if not par["bit_exact"]:
             print(f"bench: GPU results differ from the oracle at batches {par['mismatching']}", file=sys.stderr,
                   flush=True)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
         out["cpu_baseline_threads"] = cpu_baseline_threads(cfg, min(8.0, args.cpu_seconds))
         out["cpu_baseline_node"] = cpu_baseline_node(cfg, min(8.0, args.cpu_seconds))
@@ -921,6 +987,8 @@ def run_video(args, world, rank, device):
     if rank != 0:
         return None
     parts = check_video([p for r in allp for p in r], N)
+    if args.dump_outputs:  # the last pass over the video, piece by piece in frame order
+        dump_outputs(args.dump_outputs, [e for first, res in parts for e in result_arrays(f"frame{first}.", res)])
     fps = N * args.steps / elapsed
     out = {
         "metric": METRIC,
@@ -948,7 +1016,7 @@ def run_video(args, world, rank, device):
         "gathered": {"ranks": world, "pieces": len(parts), "frames": N, "whole_and_disjoint": True,
                      "transport": "gloo gather_object (host)" if world > 1 else "local"},
     }
-    if not args.no_check and not f16:
+    if args.check and not f16:
         items = [(first, res, None if first == 0 else first - 1, list(range(first, first + res["n_frames"])))
                  for first, res in parts]
         chk = oracle_check(cfg, items, chunk=50)

@@ -13,7 +13,7 @@ LIB=locomouse_cpp_amd/liblocomouse_hip.so
 cp $LIB gpurun_out/ab/orig.so
 TAG=${TAG:-combo}
 NOCHK=--no-check
-[ -n "$CHECK" ] && NOCHK=
+[ -n "$CHECK" ] && NOCHK=--full
 for rep in $(seq 1 ${REPS:-2}); do
 for v in $VARIANTS; do
   name=${v%%:*}; rest=${v#*:}; lib=${rest%%:*}; envs=${rest#*:}

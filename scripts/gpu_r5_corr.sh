@@ -17,11 +17,12 @@ if on pmc; then
   python3 scripts/pmc_clock.py gpurun_out/${PMC_TAG:-r5pmc} k_corr > gpurun_out/${PMC_TAG:-r5pmc}/clock.txt && cat gpurun_out/${PMC_TAG:-r5pmc}/clock.txt
 fi
 if on shard; then
-  mkdir -p gpurun_out/shard
+  mkdir -p ${OUT_DIR:-bench_out}/shard
   for v in ${SHARD_SHAPES:-1:4:320 1:5:256 1:4:208 1:8:160 1:6:216 2:2:320 2:4:320}; do
     IFS=: read ns nl nb <<< "$v"
-    timeout -k 10 240 python3 -u bench.py --video-frames 1250 --streams $ns --lanes $nl --batch $nb --steps 10 --warmup 3 --no-cpu > gpurun_out/shard/s_${ns}x${nl}x${nb}.json 2> gpurun_out/shard/s_${ns}x${nl}x${nb}.err || { echo "shard $v failed"; tail -5 gpurun_out/shard/s_${ns}x${nl}x${nb}.err; exit 1; }
-    python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'], d['config']['batches'], d['video_check']['bit_exact'])" gpurun_out/shard/s_${ns}x${nl}x${nb}.json
+    o=${OUT_DIR:-bench_out}/shard/s_${ns}x${nl}x${nb}
+    timeout -k 10 240 python3 -u bench.py --video-frames 1250 --streams $ns --lanes $nl --batch $nb --steps 10 --warmup 3 --full --no-cpu > $o.json 2> $o.err || { echo "shard $v failed"; tail -5 $o.err; exit 1; }
+    python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1], d['value'], d['ms_per_step'], d['config']['batches'], d['video_check']['bit_exact'])" $o.json
   done
 fi
 echo done

@@ -27,7 +27,7 @@ if on smoke; then
 fi
 bench() {  # name, args...
   local n=$1; shift
-  timeout -k 10 420 python -u bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { echo "bench $n failed"; tail -20 $O/bench_$n.err; exit 1; }
+  timeout -k 10 420 python -u bench.py --full "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { echo "bench $n failed"; tail -20 $O/bench_$n.err; exit 1; }
   python - $O/bench_$n.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

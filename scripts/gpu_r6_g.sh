@@ -11,5 +11,5 @@ timeout -k 10 700 python -u -m pytest tests/test_gpu_multiproc.py -m gpu -x -v -
 rc=$?; tail -3 $O/gpu_multiproc.log; [ $rc -eq 0 ] || { grep -E "FAIL|Error" $O/gpu_multiproc.log | head -20; exit $rc; }
 KERNELS="k_corr k_nms k_ingest k_tail k_post" bash scripts/gpu_kstats_ab.sh > $O/kstats_streams1.txt 2>&1 || { tail -5 $O/kstats_streams1.txt; exit 1; }
 grep -v "^\[" $O/kstats_streams1.txt | sort -k2,2 -k1,1
-timeout -k 10 300 python -u bench.py --video-frames 10000 --steps 5 --warmup 2 --no-cpu > $O/video_default.json 2> $O/video_default.err || { tail -5 $O/video_default.err; exit 1; }
+timeout -k 10 300 python -u bench.py --video-frames 10000 --steps 5 --warmup 2 --full --no-cpu > $O/video_default.json 2> $O/video_default.err || { tail -5 $O/video_default.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/video_default.json').read().strip().splitlines()[-1]); c=d['config']; print('video default', d['value'], d['ms_per_step'], c['contexts_per_gpu'], c['lanes_per_context'], c['batch_frames'], d['video_check']['bit_exact'])"

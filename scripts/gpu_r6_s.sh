@@ -7,7 +7,9 @@ export TMPDIR=/tmp
 for rep in 1 2 3; do
   for v in 8:448 8:512 10:448; do
     IFS=: read ns nb <<< "$v"
-    timeout -k 10 180 python3 bench.py --no-cpu --streams $ns --batch $nb --steps 40 --warmup 5 > gpurun_out/ab/r6s_${ns}x${nb}.$rep.json 2> gpurun_out/ab/r6s_${ns}x${nb}.$rep.err || { tail -5 gpurun_out/ab/r6s_${ns}x${nb}.$rep.err; exit 1; }
-    python3 -c "import json; d=json.load(open('gpurun_out/ab/r6s_${ns}x${nb}.$rep.json')); print('${ns}x${nb}', $rep, d['value'], d['roofline']['frac'], d['parity_sample']['bit_exact'])"
+    o=${OUT_DIR:-bench_out}/ab/r6s_${ns}x${nb}.$rep
+    mkdir -p ${OUT_DIR:-bench_out}/ab
+    timeout -k 10 180 python3 bench.py --full --no-cpu --streams $ns --batch $nb --steps 40 --warmup 5 > $o.json 2> $o.err || { tail -5 $o.err; exit 1; }
+    python3 -c "import json; d=json.load(open('$o.json')); print('${ns}x${nb}', $rep, d['value'], d['roofline']['frac'], d['parity_sample']['bit_exact'])"
   done
 done

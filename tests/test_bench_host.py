@@ -118,6 +118,39 @@ def test_executed_flops_counts_halo_slots():
                       2 * (w["paw_bottom"].size + w["snout_bottom"].size))
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one .npy per array (per field of a structured array),
+    float64 for integers, floats as stored; over the budget every long array is
+    cut to the same seeded sample, the same one in every run."""
+    cfg = S.SyntheticConfig()
+    ref = _oracle_video(cfg, 6)
+    named = bench.result_arrays("ctx0.", ref)
+    assert {n for n, _ in named} >= {"ctx0.cand.x", "ctx0.cand.score", "ctx0.p22d.side_count", "ctx0.tail", "ctx0.pw_pr"}
+    d = tmp_path / "whole"
+    bench.dump_outputs(str(d), named)
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n, _ in named)
+    for n, a in named:
+        got = np.load(d / (n + ".npy"))
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    f32 = np.arange(7, dtype=np.float32)
+    bench.dump_outputs(str(d), [("f32", f32)])
+    assert np.load(d / "f32.npy").dtype == np.float32
+    big = [("a", np.arange(100000, dtype=np.int32)), ("b", np.arange(10, dtype=np.float64))]
+    cut = [tmp_path / "cut0", tmp_path / "cut1"]
+    for c in cut:
+        bench.dump_outputs(str(c), big, budget=80000)
+    a0, a1 = np.load(cut[0] / "a.npy"), np.load(cut[1] / "a.npy")
+    assert np.array_equal(a0, a1) and 9000 <= a0.size <= 10000 and np.all(np.diff(a0) > 0)
+    assert np.array_equal(np.load(cut[0] / "b.npy"), big[1][1])
+    assert sum(os.path.getsize(cut[0] / f) for f in os.listdir(cut[0])) <= 80000 + 2 * 128
+
+
+def test_steps_must_be_positive():
+    p = _bench(["--gpus", "1", "--steps", "0", "--warmup", "0"], {})
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr
+    assert '"metric"' not in p.stdout
+
+
 def test_default_shape_by_mode():
     """Unset --streams / --lanes / --batch: 8 contexts x 448 frames for the C3
     resident stream (profiles/r05/sweep/), by the rank's share for one C3

@@ -74,7 +74,7 @@ def test_bench_video_mode_shards_whole_video(ranks, lanes):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--oversubscribe",
                         "--video-frames", "700", "--batch", "64", "--streams", "2", "--lanes", str(lanes),
-                        "--steps", "1", "--warmup", "1", "--no-cpu"], env=env, capture_output=True, text=True,
+                        "--steps", "1", "--warmup", "1", "--full", "--no-cpu"], env=env, capture_output=True, text=True,
                        timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -97,7 +97,7 @@ def test_bench_c4_eight_ranks_full_shape():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--oversubscribe",
-                        "--video-frames", "10000", "--steps", "1", "--warmup", "2", "--no-cpu"], env=env,
+                        "--video-frames", "10000", "--steps", "1", "--warmup", "2", "--full", "--no-cpu"], env=env,
                        capture_output=True, text=True,
                        timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
