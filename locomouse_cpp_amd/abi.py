@@ -171,6 +171,38 @@ class lm_bb_result(C.Structure):
 BB_FRAME_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y_bottom", "y_side", "width", "height_bottom", "height_side")])
 
 
+# include/locomouse_jpeg.h (device MJPEG decode)
+LM_JPEG_OK, LM_JPEG_NEEDS_HOST, LM_JPEG_REJECTED = 0, 1, 2
+LM_JPEG_SUBSEQ_MIN, LM_JPEG_SUBSEQ_DEFAULT, LM_JPEG_CHUNK = 4, 64, 128
+
+
+class lm_jpeg_info(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int32),
+        ("cols", C.c_int32),
+        ("components", C.c_int32),
+        ("h_samp", C.c_int32),
+        ("v_samp", C.c_int32),
+        ("restart_interval", C.c_int32),
+        ("status", C.c_int32),
+        ("reserved", C.c_int32),
+        ("scan_bytes", C.c_int64),
+        ("reason", C.c_char * 128),
+    ]
+
+
+class lm_jpeg_stats(C.Structure):
+    _fields_ = [
+        ("subsequences", C.c_int64),
+        ("sync_rounds", C.c_int64),
+        ("max_subsequences", C.c_int32),
+        ("max_chunk_rounds", C.c_int32),
+        ("frames_needing_host", C.c_int32),
+        ("table_sets", C.c_int32),
+        ("device_ms", C.c_double),
+    ]
+
+
 def bb_params(median_filter_size=11, min_pixel_visible=1, moving_average_window=5, connectivity=8,
               semantics=LM_BB_FIRSTLAST_AS_EXECUTED, zero_cols=(46, 760), zero_rows=(100, 149), bb_width=400,
               bb_height_side=150):

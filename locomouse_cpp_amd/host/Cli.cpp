@@ -124,6 +124,18 @@ class VideoFrames {
     decode_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return got;
   }
+  // The next (up to) n frames' chunks as they are in the file (JPEG images of an MJPEG video), appended to out.
+  int read_compressed(std::vector<std::vector<uint8_t>>& out, int n) {
+    n = (int)std::min<size_t>((size_t)std::max(n, 0), V->frame_count() - pos);
+    int got = 0;
+    for (; got < n; ++got) {
+      std::vector<uint8_t> b;
+      if (!V->read_chunk(pos + (size_t)got, b)) break;
+      out.push_back(std::move(b));
+    }
+    pos += (size_t)got;
+    return got;
+  }
   int threads() const { return T; }
   double decode_s = 0;  // wall seconds in read(dst, n): file reads + decoding on T threads
   void rewind() { pos = 0; }  // V.set(CV_CAP_PROP_POS_FRAMES, 0)
@@ -323,6 +335,21 @@ int run(int argc, char** argv) {
   li.read_frame = [reader](uint8_t* dst) { return reader->read(dst); };
   li.read_frames = [reader](uint8_t* dst, int n) { return reader->read(dst, n); };
   li.rewind = [reader] { reader->rewind(); };
+  // LM_DECODE=host|device: where MJPEG frames are decoded (LocoMouse_Inputs::decode); unset means host
+  if (const char* dm = std::getenv("LM_DECODE")) {
+    const std::string v = dm;
+    if (v == "device") {
+      if (!video->is_mjpeg())
+        throw std::invalid_argument("LM_DECODE=device needs an MJPEG video (MJPG / JPEG / AVI1): " + in.VIDEO_FILE +
+                                    " is not one.");
+      li.decode = LocoMouse_Inputs::Decode::device;
+      li.read_compressed = [reader](std::vector<std::vector<uint8_t>>& out, int n) {
+        return reader->read_compressed(out, n);
+      };
+    } else if (v != "host" && !v.empty()) {
+      throw std::invalid_argument("LM_DECODE must be host or device, not " + v + ".");
+    }
+  }
   li.output_file = in.OUTPUT_PATH + "/output_" + in.FILE_STEM + ".yml";
   if (const char* d = std::getenv("LM_DEVICE")) li.device = std::atoi(d);
   // LM_DEVICES=0,1,...: detection sharded over these GPUs (LocoMouse_Inputs::devices);
@@ -415,7 +442,8 @@ int run(int argc, char** argv) {
               << ms(t_loop, t_tracks) << " export_ms " << ms(t_tracks, std::chrono::steady_clock::now())
               << " decode_ms " << 1e3 * (reader->decode_s - decode_init) << " decode_threads " << reader->threads()
               << " submit_ms " << 1e3 * st.submit_s << " wait_ms " << 1e3 * st.wait_s << " batches " << st.batches
-              << " frames " << L->N_frames() << std::endl;
+              << " frames " << L->N_frames() << " decode_device_ms " << 1e3 * st.decode_device_s
+              << " decode_fallback_frames " << st.decode_fallback_frames << std::endl;
   }
   return EXIT_SUCCESS;
 }

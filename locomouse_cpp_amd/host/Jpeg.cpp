@@ -9,79 +9,19 @@
 // the reference's OpenCV build links for still images.
 #include "Jpeg.hpp"
 
+#include "../csrc/lm_jpeg_hdr.h"
+
 #include <algorithm>
 #include <cstring>
 
 namespace locomouse {
 namespace {
 
-// Zig-zag scan position -> natural (row-major) coefficient index, padded so a
-// corrupt run length past 63 lands on a harmless slot.
-constexpr uint8_t kNatural[64 + 16] = {
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,
-    6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
-    39, 46, 53, 60, 61, 54, 47, 55, 62, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
-
-// ITU-T T.81 Annex K.3 tables (what MJPEG "AVI1" frames leave out).
-constexpr uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-constexpr uint8_t kDcChromBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-constexpr uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-constexpr uint8_t kAcLumBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
-constexpr uint8_t kAcLumVals[162] = {
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
-    0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
-    0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
-    0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
-    0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
-    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
-    0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
-    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-constexpr uint8_t kAcChromBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
-constexpr uint8_t kAcChromVals[162] = {
-    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
-    0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
-    0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
-    0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
-    0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
-    0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
-    0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
-    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-
-constexpr int kLook = 9;  // Huffman lookahead bits
-
-// Canonical Huffman table (T.81 C.2 / F.2.2.3) with a 9-bit lookahead.
-struct Huff {
-  bool defined = false;
-  uint16_t look[1 << kLook];  // (length << 8) | symbol; 0 = longer code
-  int32_t maxcode[18];        // largest code of each length, -1 if none
-  int32_t valoff[17];         // symbol index = code + valoff[length]
-  uint8_t vals[256];
-};
-
-bool build_huff(Huff& h, const uint8_t bits[16], const uint8_t* vals, int nvals) {
-  int total = 0;
-  for (int l = 0; l < 16; ++l) total += bits[l];
-  if (total > 256 || total > nvals) return false;
-  std::memset(h.look, 0, sizeof(h.look));
-  std::memcpy(h.vals, vals, (size_t)total);
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; ++l) {
-    h.valoff[l] = k - code;
-    for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code)
-      if (l <= kLook) {
-        const int sh = kLook - l;
-        for (int j = 0; j < (1 << sh); ++j) h.look[(code << sh) | j] = (uint16_t)((l << 8) | vals[k]);
-      }
-    h.maxcode[l] = bits[l - 1] ? code - 1 : -1;
-    if (bits[l - 1] && code >= (1 << l)) return false;  // over-subscribed (or an all-ones code)
-    code <<= 1;
-  }
-  h.maxcode[17] = 0x7FFFFFFF;
-  h.defined = true;
-  return true;
-}
+// Header parsing, the Huffman tables and the zig-zag order are shared with the
+// device decoder (csrc/lm_jpeg_hdr.h).
+using lmj::kNatural;
+using Huff = lmj::HuffTable;
+constexpr int kLook = LMJ_LOOK;  // Huffman lookahead bits
 
 // Entropy-coded segment reader: byte stuffing (FF 00) removed, fill bytes
 // (FF FF ..) skipped, stops at a marker and feeds zeros past it (libjpeg's
@@ -292,107 +232,15 @@ struct CbToB {
 };
 const CbToB kCbB;
 
-struct Component {
-  int id = 0, h = 1, v = 1, tq = 0;
-  int td = 0, ta = 0;      // scan tables
-  int dw = 0, dh = 0;      // downsampled size (jdinput.c: ceil(W * h / Hmax))
-  int pitch = 0, prows = 0;
+struct Component : lmj::CompBase {
   int pred = 0;
   bool need = false;       // plane feeds channel 0
   std::vector<uint8_t> plane;
 };
 
-struct Decoder {
-  uint16_t qt[4][64];
-  bool qdef[4] = {false, false, false, false};
-  Huff dc[4], ac[4];
-  int W = 0, H = 0, nc = 0, hmax = 1, vmax = 1, restart = 0;
-  bool sof = false, jfif = false, adobe = false;
-  int adobe_transform = -1;
-  Component comp[3];
-  std::string why;
-
-  bool fail(const char* m) {
-    why = m;
-    return false;
-  }
-
-  static int u16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
-
-  bool parse_dqt(const uint8_t* p, int n) {
-    while (n > 0) {
-      const int pq = p[0] >> 4, tq = p[0] & 15;
-      const int sz = 1 + 64 * (pq ? 2 : 1);
-      if (tq > 3 || pq > 1 || n < sz) return fail("bad DQT segment");
-      for (int k = 0; k < 64; ++k) qt[tq][kNatural[k]] = (uint16_t)(pq ? u16(p + 1 + 2 * k) : p[1 + k]);
-      qdef[tq] = true;
-      p += sz;
-      n -= sz;
-    }
-    return true;
-  }
-
-  bool parse_dht(const uint8_t* p, int n) {
-    while (n > 0) {
-      if (n < 17) return fail("bad DHT segment");
-      const int tc = p[0] >> 4, th = p[0] & 15;
-      int total = 0;
-      for (int l = 0; l < 16; ++l) total += p[1 + l];
-      if (tc > 1 || th > 3 || total > 256 || n < 17 + total) return fail("bad DHT segment");
-      if (!build_huff(tc ? ac[th] : dc[th], p + 1, p + 17, total)) return fail("bad Huffman table");
-      p += 17 + total;
-      n -= 17 + total;
-    }
-    return true;
-  }
-
-  bool parse_sof(const uint8_t* p, int n) {
-    if (sof) return fail("more than one frame header");
-    if (n < 6) return fail("bad SOF segment");
-    if (p[0] != 8) return fail("only 8-bit JPEG samples are supported");
-    H = u16(p + 1);
-    W = u16(p + 3);
-    nc = p[5];
-    if (W <= 0 || H <= 0) return fail("JPEG image of zero size (DNL not supported)");
-    if (nc != 1 && nc != 3) return fail("only 1- or 3-component JPEG images are supported");
-    if (n < 6 + 3 * nc) return fail("bad SOF segment");
-    hmax = vmax = 1;
-    for (int c = 0; c < nc; ++c) {
-      Component& C = comp[c];
-      C.id = p[6 + 3 * c];
-      C.h = p[7 + 3 * c] >> 4;
-      C.v = p[7 + 3 * c] & 15;
-      C.tq = p[8 + 3 * c];
-      if (C.h < 1 || C.h > 4 || C.v < 1 || C.v > 4 || C.tq > 3) return fail("bad JPEG component parameters");
-      hmax = std::max(hmax, C.h);
-      vmax = std::max(vmax, C.v);
-    }
-    const int mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-    for (int c = 0; c < nc; ++c) {
-      Component& C = comp[c];
-      C.dw = (W * C.h + hmax - 1) / hmax;
-      C.dh = (H * C.v + vmax - 1) / vmax;
-      C.pitch = mcux * C.h * 8;
-      C.prows = mcuy * C.v * 8;
-    }
-    sof = true;
-    return true;
-  }
-
-  // Colour space as libjpeg's default_decompress_parms picks it.
-  bool is_rgb() const {
-    if (nc != 3) return false;
-    if (jfif) return false;
-    if (adobe) return adobe_transform == 0;
-    return comp[0].id == 'R' && comp[1].id == 'G' && comp[2].id == 'B';
-  }
-
-  void fill_default_tables() {
-    if (!dc[0].defined) build_huff(dc[0], kDcLumBits, kDcVals, 12);
-    if (!dc[1].defined) build_huff(dc[1], kDcChromBits, kDcVals, 12);
-    if (!ac[0].defined) build_huff(ac[0], kAcLumBits, kAcLumVals, 162);
-    if (!ac[1].defined) build_huff(ac[1], kAcChromBits, kAcChromVals, 162);
-  }
+// The segment walk and its state are lmj::HeaderState's; this adds the scans.
+struct Decoder : lmj::HeaderState<Component> {
+  std::vector<int16_t>* coef_sink = nullptr;  // tests: every block's coefficients, in decoding order
 
   void decode_block(Bits& b, Component& C, int16_t* blk) {
     std::memset(blk, 0, 64 * sizeof(int16_t));
@@ -442,6 +290,7 @@ struct Decoder {
           for (int v = 0; v < bv; ++v)
             for (int h = 0; h < bh; ++h) {
               decode_block(b, C, blk);
+              if (coef_sink) coef_sink->insert(coef_sink->end(), blk, blk + 64);
               if (!C.need) continue;
               const int bx = mx * bh + h, by = my * bv + v;
               idct_islow(blk, qt[C.tq], C.plane.data() + (size_t)by * 8 * C.pitch + bx * 8, C.pitch);
@@ -457,90 +306,27 @@ struct Decoder {
   }
 
   bool run(const uint8_t* d, size_t n) {
-    const uint8_t* end = d + n;
-    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail("not a JPEG image (no SOI)");
-    const uint8_t* p = d + 2;
-    bool scanned = false;
-    for (;;) {
-      while (p < end && *p != 0xFF) ++p;  // garbage between segments
-      while (p < end && *p == 0xFF) ++p;
-      if (p >= end) break;
-      const int m = *p++;
-      if (m == 0xD9) break;                         // EOI
-      if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;  // TEM / stray RSTn
-      if (m == 0xD8) return fail("nested SOI");
-      if (end - p < 2) return fail("truncated JPEG segment");
-      const int len = u16(p);
-      if (len < 2 || end - p < len) return fail("truncated JPEG segment");
-      const uint8_t* s = p + 2;
-      const int sn = len - 2;
-      p += len;
-      switch (m) {
-        case 0xC0:
-        case 0xC1:
-          if (!parse_sof(s, sn)) return false;
-          break;
-        case 0xC2: case 0xC3: case 0xC5: case 0xC6: case 0xC7:
-        case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-          return fail("only sequential Huffman JPEG is supported (progressive/lossless/arithmetic found)");
-        case 0xC4:
-          if (!parse_dht(s, sn)) return false;
-          break;
-        case 0xDB:
-          if (!parse_dqt(s, sn)) return false;
-          break;
-        case 0xDD:
-          if (sn < 2) return fail("bad DRI segment");
-          restart = u16(s);
-          break;
-        case 0xE0:
-          if (sn >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) jfif = true;
-          break;
-        case 0xEE:
-          if (sn >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
-            adobe = true;
-            adobe_transform = s[11];
-          }
-          break;
-        case 0xDA: {
-          if (!sof) return fail("scan before frame header");
-          if (sn < 1) return fail("bad SOS segment");
-          const int ns = s[0];
-          if (ns < 1 || ns > nc || sn < 1 + 2 * ns + 3) return fail("bad SOS segment");
-          int idx[3];
-          for (int i = 0; i < ns; ++i) {
-            const int cid = s[1 + 2 * i];
-            int c = 0;
-            while (c < nc && comp[c].id != cid) ++c;
-            if (c == nc) return fail("scan names an unknown component");
-            idx[i] = c;
-            comp[c].td = s[2 + 2 * i] >> 4;
-            comp[c].ta = s[2 + 2 * i] & 15;
-            if (comp[c].td > 3 || comp[c].ta > 3) return fail("bad SOS table selector");
-          }
-          if (!scanned) {  // first scan: decide which planes channel 0 needs
-            const bool rgb = is_rgb();
-            for (int c = 0; c < nc; ++c) {
-              comp[c].need = nc == 1 || (rgb ? c == 2 : c <= 1);
-              if (comp[c].need) comp[c].plane.assign((size_t)comp[c].pitch * comp[c].prows, 0);
-            }
-          }
-          fill_default_tables();
-          for (int i = 0; i < ns; ++i) {
-            const Component& C = comp[idx[i]];
-            if (!dc[C.td].defined || !ac[C.ta].defined) return fail("scan uses an undefined Huffman table");
-            if (C.need && !qdef[C.tq]) return fail("component uses an undefined quantisation table");
-          }
-          p = decode_scan(p, end, ns, idx);
-          scanned = true;
-          break;
+    return walk(d, n, [this](const uint8_t* p, const uint8_t* end, int ns, const int* idx, bool first) {
+      if (first) {  // first scan: decide which planes channel 0 needs
+        for (int c = 0; c < nc; ++c) {
+          comp[c].need = needed(c);
+          if (comp[c].need) comp[c].plane.assign((size_t)comp[c].pitch * comp[c].prows, 0);
         }
-        default:
-          break;  // APPn, COM, DNL, ...
       }
-    }
-    if (!scanned) return fail("JPEG image has no scan");
-    return true;
+      fill_default_tables();
+      for (int i = 0; i < ns; ++i) {
+        const Component& C = comp[idx[i]];
+        if (!dc[C.td].defined || !ac[C.ta].defined) {
+          fail("scan uses an undefined Huffman table");
+          return (const uint8_t*)nullptr;
+        }
+        if (C.need && !qdef[C.tq]) {
+          fail("component uses an undefined quantisation table");
+          return (const uint8_t*)nullptr;
+        }
+      }
+      return decode_scan(p, end, ns, idx);
+    });
   }
 
   // Plane row y of component C at full resolution (upsampled by libjpeg's
@@ -649,6 +435,17 @@ bool decode_jpeg_channel0(const uint8_t* data, size_t size, int& rows, int& cols
   cols = D.W;
   out.resize((size_t)rows * cols);
   D.channel0(out.data());
+  return true;
+}
+
+bool decode_jpeg_coefficients(const uint8_t* data, size_t size, std::vector<int16_t>& coef, std::string* err) {
+  Decoder D;
+  coef.clear();
+  D.coef_sink = &coef;
+  if (!D.run(data, size)) {
+    if (err) *err = D.why;
+    return false;
+  }
   return true;
 }
 

@@ -41,6 +41,11 @@ bool decode_jpeg_channel0(const uint8_t* data, size_t size, int& rows, int& cols
 bool decode_jpeg_channel0_into(const uint8_t* data, size_t size, int rows, int cols, uint8_t* out,
                                std::string* err = nullptr);
 
+// Test access: the quantised coefficients the decoder feeds its IDCT — every
+// block of every scan in decoding order, 64 int16 each, natural order, DC
+// already predicted (Cr blocks included, though channel 0 never uses them).
+bool decode_jpeg_coefficients(const uint8_t* data, size_t size, std::vector<int16_t>& coef, std::string* err = nullptr);
+
 }  // namespace locomouse
 
 #endif

@@ -3,6 +3,9 @@
 // method cites the reference code whose observable behaviour it keeps.
 #include "LocoMouse.hpp"
 
+#include "Jpeg.hpp"
+#include "locomouse_jpeg.h"
+
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -140,6 +143,67 @@ void throw_on_error(lm_status s) {
   throw std::runtime_error(lm_last_error());
 }
 
+// ------------------------------------------------ device decode (MJPEG)
+//
+// One lm_jpeg_ctx and a ring of device frame buffers: a batch of compressed
+// frames is decoded into the next buffer of the ring, where it stays until
+// its detection batch has been collected (at most 2 x lanes batches wait for
+// collection, so 2 x lanes + 1 buffers never wrap onto a live one).  Frames
+// the device hands back are decoded by the host decoder and copied in.
+struct LocoMouse::DeviceJpeg {
+  lm_jpeg_ctx* ctx = nullptr;
+  std::vector<uint8_t*> slots;
+  size_t next = 0;
+  int rows, cols;
+  size_t frame_bytes;
+  std::vector<uint8_t> tmp;
+
+  DeviceJpeg(int device, int rows_, int cols_, int max_frames, int n_slots)
+      : rows(rows_), cols(cols_), frame_bytes((size_t)rows_ * cols_) {
+    throw_on_error(lm_jpeg_create(device, rows, cols, max_frames, 0, &ctx));
+    try {
+      for (int i = 0; i < n_slots; ++i) {
+        uint8_t* d = nullptr;
+        throw_on_error(lm_jpeg_device_alloc(ctx, frame_bytes * (size_t)max_frames, &d));
+        slots.push_back(d);
+      }
+    } catch (...) {
+      lm_jpeg_destroy(ctx);
+      throw;
+    }
+  }
+  ~DeviceJpeg() { lm_jpeg_destroy(ctx); }  // frees the slots
+  DeviceJpeg(const DeviceJpeg&) = delete;
+  DeviceJpeg& operator=(const DeviceJpeg&) = delete;
+
+  // The frames into the ring's next buffer; returns its device address.
+  uint8_t* decode(const std::vector<const std::vector<uint8_t>*>& frames, double& secs, int& fallbacks) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n = (int)frames.size();
+    std::vector<const uint8_t*> ptr((size_t)n);
+    std::vector<size_t> size((size_t)n);
+    std::vector<int32_t> status((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      ptr[i] = frames[i]->data();
+      size[i] = frames[i]->size();
+      if (!ptr[i] || !size[i]) throw std::runtime_error("Error: Failed to read image from video file.\n");
+    }
+    uint8_t* d = slots[next];
+    next = (next + 1) % slots.size();
+    throw_on_error(lm_jpeg_decode_device(ctx, ptr.data(), size.data(), n, d, (int64_t)frame_bytes, status.data()));
+    for (int i = 0; i < n; ++i) {
+      if (status[i] == LM_JPEG_OK) continue;
+      tmp.resize(frame_bytes);
+      if (!decode_jpeg_channel0_into(ptr[i], size[i], rows, cols, tmp.data()))
+        throw std::runtime_error("Error: Failed to read image from video file.\n");  // as a failed V >> F
+      throw_on_error(lm_jpeg_upload(ctx, d + (size_t)i * frame_bytes, tmp.data(), frame_bytes));
+      ++fallbacks;
+    }
+    secs += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return d;
+  }
+};
+
 // ------------------------------------------------------- multi-GPU shards
 //
 // main.cpp:54-82 is a loop over frames whose only cross-frame state is the
@@ -156,6 +220,11 @@ struct LocoMouse::DevicePool {
   struct Job {
     int first = 0, n = 0;
     uint8_t* frames = nullptr;     // pinned batch buffer (returned to the pool once submitted)
+    // Decode::device instead of `frames`: the batch's JPEG images, preceded by the halo frame's when there is one
+    std::vector<std::vector<uint8_t>> jpegs;
+    bool jpeg_halo = false;
+    double decode_s = 0;           // set by the device thread before `done`
+    int fallbacks = 0;
     std::vector<uint8_t> halo;     // frame first-1 (empty for the video's first batch)
     std::vector<int32_t> bb;       // per-frame corners, halo frame first when present
     std::promise<std::unique_ptr<FrameResults>> done;
@@ -163,6 +232,7 @@ struct LocoMouse::DevicePool {
   struct Worker {
     int device = 0;
     lm_ctx* ctx = nullptr;
+    std::unique_ptr<DeviceJpeg> jpeg;  // Decode::device
     std::thread th;
     std::mutex m;
     std::condition_variable cv;
@@ -178,16 +248,19 @@ struct LocoMouse::DevicePool {
   std::vector<uint8_t*> free_bufs;
   std::vector<uint8_t*> all_bufs;
   std::deque<std::future<std::unique_ptr<FrameResults>>> results;  // oldest batch first
+  std::deque<std::shared_ptr<Job>> jobs;                            // the same batches (their decode times)
   size_t next = 0;                                                  // the next batch's worker
 
   DevicePool(const std::vector<int>& devices, const lm_setup& setup, const lm_params& params, const lm_model& model,
-             int batch_, size_t frame_bytes_)
+             int batch_, size_t frame_bytes_, bool device_decode)
       : frame_bytes(frame_bytes_), batch(batch_), lanes(std::max(1, setup.pipeline_lanes)) {
     try {
       for (int d : devices) {
         auto w = std::make_unique<Worker>();
         w->device = d;
         throw_on_error(lm_ctx_create(d, &setup, &params, &model, batch, &w->ctx));
+        if (device_decode)  // a halo frame travels with its batch: batch + 1 frames per buffer
+          w->jpeg = std::make_unique<DeviceJpeg>(d, setup.video_rows, setup.video_cols, batch + 1, 2 * lanes + 1);
         workers.push_back(std::move(w));
       }
       // two buffers per device: one being filled by the reader while another waits for its worker
@@ -216,11 +289,13 @@ struct LocoMouse::DevicePool {
     release();
   }
   void release() {
-    for (auto& w : workers)
+    for (auto& w : workers) {
       if (w->ctx) {
         lm_ctx_destroy(w->ctx);
         w->ctx = nullptr;
       }
+      w->jpeg.reset();
+    }
     for (uint8_t* p : all_bufs) lm_host_free(p);
     all_bufs.clear();
   }
@@ -244,6 +319,7 @@ struct LocoMouse::DevicePool {
 
   void submit(std::shared_ptr<Job> j) {
     results.push_back(j->done.get_future());
+    jobs.push_back(j);
     Worker& w = *workers[next];
     next = (next + 1) % workers.size();
     {
@@ -263,7 +339,8 @@ struct LocoMouse::DevicePool {
         std::unique_lock<std::mutex> g(w.m);
         w.cv.wait(g, [&] { return w.stop || !w.queue.empty() || !inflight.empty(); });
         if (w.stop) {  // the object is going away: batches not yet submitted are dropped
-          for (auto& q : w.queue) give_buffer(q->frames);
+          for (auto& q : w.queue)
+            if (q->frames) give_buffer(q->frames);
           w.queue.clear();
         }
         if (!w.queue.empty() && (int)inflight.size() < 2 * lanes) {
@@ -275,12 +352,22 @@ struct LocoMouse::DevicePool {
       }
       if (j) {
         try {
-          throw_on_error(lm_detect_submit(w.ctx, j->frames, (int64_t)frame_bytes, j->n, j->first,
-                                          j->halo.empty() ? nullptr : j->halo.data(), j->bb.data()));
-          give_buffer(j->frames);
+          if (w.jpeg) {
+            std::vector<const std::vector<uint8_t>*> fr;
+            for (const auto& q : j->jpegs) fr.push_back(&q);
+            uint8_t* d = w.jpeg->decode(fr, j->decode_s, j->fallbacks);
+            const int h = j->jpeg_halo ? 1 : 0;
+            j->jpegs.clear();
+            throw_on_error(lm_detect_submit_device(w.ctx, d + (size_t)h * frame_bytes, (int64_t)frame_bytes, j->n,
+                                                   j->first, h ? d : nullptr, j->bb.data()));
+          } else {
+            throw_on_error(lm_detect_submit(w.ctx, j->frames, (int64_t)frame_bytes, j->n, j->first,
+                                            j->halo.empty() ? nullptr : j->halo.data(), j->bb.data()));
+            give_buffer(j->frames);
+          }
           inflight.push_back(std::move(j));
         } catch (...) {
-          give_buffer(j->frames);
+          if (j->frames) give_buffer(j->frames);
           j->done.set_exception(std::current_exception());
         }
         continue;
@@ -308,7 +395,12 @@ void move_append(std::vector<T>& dst, std::vector<T>& src) {
 }  // namespace
 
 LocoMouse::LocoMouse(const LocoMouse_Inputs& inputs) : IN(inputs), METHOD(0), N_FRAMES(inputs.n_frames) {
-  if (!IN.read_frame && !IN.read_frames) throw std::invalid_argument("LocoMouse: no frame reader (V) given.");
+  if (IN.decode == LocoMouse_Inputs::Decode::device) {
+    if (!IN.read_compressed)
+      throw std::invalid_argument("LocoMouse: device decode needs a compressed frame source (read_compressed).");
+  } else if (!IN.read_frame && !IN.read_frames) {
+    throw std::invalid_argument("LocoMouse: no frame reader (V) given.");
+  }
   if (IN.batch < 1) throw std::invalid_argument("LocoMouse: batch must be >= 1.");
   if (IN.setup.video_rows <= 0 || IN.setup.video_cols <= 0)
     throw std::invalid_argument("LocoMouse: video size must be positive.");
@@ -374,9 +466,24 @@ void LocoMouse::runBoundingBoxPass(int method) {
   lm_bb_ctx* raw = nullptr;
   throw_on_error(lm_bb_create(IN.device, &su, &IN.bb_params, IN.batch, &raw));
   std::unique_ptr<lm_bb_ctx, void (*)(lm_bb_ctx*)> bb(raw, lm_bb_destroy);
-  std::vector<uint8_t> buf(FRAME_BYTES * (size_t)IN.batch);
+  const bool on_device = IN.decode == LocoMouse_Inputs::Decode::device;
+  std::unique_ptr<DeviceJpeg> dec;
+  if (on_device) dec = std::make_unique<DeviceJpeg>(IN.device, IN.setup.video_rows, IN.setup.video_cols, IN.batch, 1);
+  std::vector<uint8_t> buf(on_device ? 0 : FRAME_BYTES * (size_t)IN.batch);
+  std::vector<std::vector<uint8_t>> jp;
   for (unsigned done = 0; done < N_FRAMES;) {
     const int n = (int)std::min<unsigned>((unsigned)IN.batch, N_FRAMES - done);
+    if (on_device) {  // compressed frames up, decoded frames stay on the device (lm_bb_push_device waits for its kernels)
+      jp.clear();
+      if (IN.read_compressed(jp, n) != n || (int)jp.size() != n)
+        throw std::runtime_error("Error: Failed to read image from video file.\n");
+      std::vector<const std::vector<uint8_t>*> fr;
+      for (const auto& q : jp) fr.push_back(&q);
+      uint8_t* d = dec->decode(fr, TIMES.decode_device_s, TIMES.decode_fallback_frames);
+      throw_on_error(lm_bb_push_device(bb.get(), d, (int64_t)FRAME_BYTES, n, nullptr));
+      done += (unsigned)n;
+      continue;
+    }
     if (IN.read_frames) {
       if (IN.read_frames(buf.data(), n) != n) throw std::runtime_error("Error: Failed to read image from video file.\n");
     } else {
@@ -415,14 +522,20 @@ void LocoMouse::initializeFeatureLoop() {
                << "BB_BOTTOM_MOUSE: " << debug_rect(BB_BOTTOM_MOUSE) << std::endl;
   IN.setup.pipeline_lanes = std::max(1, std::min(IN.lanes, LM_MAX_LANES));
   if (IN.devices.size() > 1) {
-    POOL = std::make_unique<DevicePool>(IN.devices, IN.setup, IN.params, IN.model, IN.batch, FRAME_BYTES);
+    POOL = std::make_unique<DevicePool>(IN.devices, IN.setup, IN.params, IN.model, IN.batch, FRAME_BYTES,
+                                        IN.decode == LocoMouse_Inputs::Decode::device);
     CTX = POOL->first_ctx();
     PENDING.p = POOL->take_buffer();  // pool-owned: handed to the workers and swapped at every flush
   } else {
     throw_on_error(lm_ctx_create(IN.device, &IN.setup, &IN.params, &IN.model, IN.batch, &CTX));
-    PENDING.allocate(FRAME_BYTES * (size_t)IN.batch);
+    if (IN.decode == LocoMouse_Inputs::Decode::device)
+      JPEG = std::make_unique<DeviceJpeg>(IN.device, IN.setup.video_rows, IN.setup.video_cols, IN.batch,
+                                          2 * lm_ctx_lanes(CTX) + 1);
+    else
+      PENDING.allocate(FRAME_BYTES * (size_t)IN.batch);
   }
   N_PENDING = 0;
+  CPENDING.clear();
   if (DEBUG_TEXT.is_open()) {  // :700-704, :766
     const lm_geometry g = geometry();
     DEBUG_TEXT << "M_size_pre_side().height, M_size_pre_bottom().height: " << g.spre_t_h << " " << g.spre_b_h
@@ -446,6 +559,15 @@ void LocoMouse::readFrame() {
   if (!CTX) throw std::runtime_error("readFrame: initializeFeatureLoop() has not been called.");
   if (N_PENDING == IN.batch) flush();  // a caller that skips storePreviousImage
   const unsigned left = N_FRAMES - (unsigned)(CURRENT_FRAME + 1);
+  if (IN.decode == LocoMouse_Inputs::Decode::device) {  // a batch of compressed frames ahead; decoded when handed over
+    if ((int)CPENDING.size() == N_PENDING && left > 0)
+      IN.read_compressed(CPENDING, (int)std::min<unsigned>((unsigned)(IN.batch - N_PENDING), left));
+    if (!(left > 0 && N_PENDING < (int)CPENDING.size()))
+      throw std::runtime_error("Error: Failed to read image from video file.\n");  // :1284-1286
+    ++N_PENDING;
+    ++CURRENT_FRAME;
+    return;
+  }
   if (IN.read_frames && N_PENDING == N_READ_AHEAD && left > 0) {
     const int want = (int)std::min<unsigned>((unsigned)(IN.batch - N_PENDING), left);
     N_READ_AHEAD += std::max(0, IN.read_frames(PENDING.data() + (size_t)N_PENDING * FRAME_BYTES, want));
@@ -501,7 +623,11 @@ void LocoMouse::collect_oldest() {
   if (POOL) {  // the batch's device thread collected it into a chunk of containers
     auto fut = std::move(POOL->results.front());
     POOL->results.pop_front();
+    std::shared_ptr<DevicePool::Job> job = std::move(POOL->jobs.front());
+    POOL->jobs.pop_front();
     std::unique_ptr<FrameResults> R = fut.get();
+    TIMES.decode_device_s += job->decode_s;
+    TIMES.decode_fallback_frames += job->fallbacks;
     move_append(CANDIDATES_BOTTOM_PAW, R->CANDIDATES_BOTTOM_PAW);
     move_append(CANDIDATES_BOTTOM_SNOUT, R->CANDIDATES_BOTTOM_SNOUT);
     move_append(CANDIDATES_SIDE_PAW, R->CANDIDATES_SIDE_PAW);
@@ -548,6 +674,34 @@ void LocoMouse::flush() {
   // numbering stay in step.
   const int ahead = std::max(0, N_READ_AHEAD - n);
   ++TIMES.batches;
+  if (IN.decode == LocoMouse_Inputs::Decode::device) {
+    if (POOL) {
+      while (INFLIGHT.size() >= POOL->capacity()) collect_oldest();
+      auto j = std::make_shared<DevicePool::Job>();
+      j->first = first;
+      j->n = n;
+      j->bb = std::move(bb);
+      j->jpeg_halo = h != 0;
+      if (h) j->jpegs.push_back(LAST_JPEG);
+      LAST_JPEG = CPENDING[(size_t)n - 1];
+      for (int i = 0; i < n; ++i) j->jpegs.push_back(std::move(CPENDING[(size_t)i]));
+      const auto t0 = std::chrono::steady_clock::now();
+      POOL->submit(std::move(j));
+      TIMES.submit_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+      while ((int)INFLIGHT.size() >= 2 * lm_ctx_lanes(CTX)) collect_oldest();
+      std::vector<const std::vector<uint8_t>*> fr;
+      for (int i = 0; i < n; ++i) fr.push_back(&CPENDING[(size_t)i]);
+      uint8_t* d = JPEG->decode(fr, TIMES.decode_device_s, TIMES.decode_fallback_frames);
+      const auto t0 = std::chrono::steady_clock::now();
+      throw_on_error(lm_detect_submit_device(CTX, d, (int64_t)FRAME_BYTES, n, first, nullptr, bb.data()));
+      TIMES.submit_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    INFLIGHT.push_back({first, n});
+    CPENDING.erase(CPENDING.begin(), CPENDING.begin() + n);  // frames read ahead past this batch stay
+    N_PENDING = 0;
+    return;
+  }
   if (POOL) {
     while (INFLIGHT.size() >= POOL->capacity()) collect_oldest();
     auto j = std::make_shared<DevicePool::Job>();

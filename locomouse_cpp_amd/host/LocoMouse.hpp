@@ -64,6 +64,18 @@ struct LocoMouse_Inputs {
   // missing frame is consumed.  Frames read ahead survive a batch handed over
   // early (a result accessor called mid-batch).
   std::function<int(uint8_t* dst, int n)> read_frames;
+  // Optional, for MJPEG videos: the next (up to) n frames as their JPEG bytes,
+  // appended to `out`; returns how many were read (fewer than n only at the
+  // end of the video or on a read error).  It shares the read position with
+  // read_frame / read_frames and `rewind`.  Used when decode == Decode::device:
+  // batches then go to the device compressed (lm_jpeg_decode_device) and the
+  // decoded frames stay in device memory for lm_detect_submit_device /
+  // lm_bb_push_device.  A frame the device hands back (LM_JPEG_NEEDS_HOST) is
+  // decoded by decode_jpeg_channel0_into and copied into its slot, so results
+  // never depend on the choice.
+  std::function<int(std::vector<std::vector<uint8_t>>& out, int n)> read_compressed;
+  enum class Decode { host, device };
+  Decode decode = Decode::host;
   int device = 0;      // HIP device of this instance (one per GPU / host thread)
   int batch = 256;     // frames per lm_detect_submit / lm_bb_push call
   int lanes = 4;       // batches in flight on the device (lm_setup.pipeline_lanes)
@@ -148,6 +160,11 @@ class LocoMouse : protected FrameResults {
   struct StageTimes {
     double submit_s = 0, wait_s = 0;
     int batches = 0;
+    // Decode::device: wall seconds in the device decode (upload, kernels,
+    // host fallbacks; on a device thread with several devices), and the
+    // frames the host decoder had to take.
+    double decode_device_s = 0;
+    int decode_fallback_frames = 0;
   };
   StageTimes stage_times() const { return TIMES; }
 
@@ -177,6 +194,10 @@ class LocoMouse : protected FrameResults {
   lm_ctx* CTX = nullptr;  // the (first) device's context
   struct DevicePool;      // per-device contexts and host threads of a multi-GPU run
   std::unique_ptr<DevicePool> POOL;
+  struct DeviceJpeg;      // Decode::device: an lm_jpeg_ctx and its ring of device frame buffers
+  std::unique_ptr<DeviceJpeg> JPEG;
+  std::vector<std::vector<uint8_t>> CPENDING;  // Decode::device: compressed frames read but not yet submitted
+  std::vector<uint8_t> LAST_JPEG;              // multi-GPU: the last compressed frame handed over (the next halo)
   std::vector<uint8_t> LAST_FRAME;  // multi-GPU: the last raw frame handed over, the next shard's halo
  protected:
   void runBoundingBoxPass(int method);  // lm_bb_* over the whole video, then rewind

@@ -187,6 +187,18 @@ bool AviReader::read(uint8_t* channel0) {
   return read_at(next_++, channel0);
 }
 
+bool AviReader::read_chunk(size_t index, std::vector<uint8_t>& bytes) const {
+  if (!f_ || index >= frames_.size()) return false;
+  const auto fr = frames_[index];
+  bytes.resize(fr.second);
+  for (size_t got = 0; got < fr.second;) {
+    const ssize_t r = pread(fileno(f_), bytes.data() + got, fr.second - got, (off_t)(fr.first + (long)got));
+    if (r <= 0) return false;
+    got += (size_t)r;
+  }
+  return true;
+}
+
 bool AviReader::read_at(size_t index, uint8_t* channel0) const {
   if (!f_ || index >= frames_.size()) return false;
   const auto fr = frames_[index];

@@ -42,6 +42,11 @@ class AviReader {
   // Frame `index` (0-based) without moving the read position; safe to call
   // from several threads at once (pread on the file descriptor).
   bool read_at(size_t index, uint8_t* channel0) const;
+  // MJPEG ('MJPG'/'JPEG'/'AVI1'): every frame chunk is one JPEG image.
+  bool is_mjpeg() const { return mjpeg_; }
+  // The raw bytes of frame `index`'s chunk (a JPEG image when is_mjpeg()),
+  // without moving the read position; thread-safe like read_at.
+  bool read_chunk(size_t index, std::vector<uint8_t>& bytes) const;
 
  private:
   std::FILE* f_ = nullptr;

@@ -10,7 +10,8 @@ import subprocess
 
 import numpy as np
 
-from .abi import BB_FRAME_DTYPE, LM_OK, lm_batch_result, lm_bb_result, lm_geometry, result_to_numpy
+from .abi import (BB_FRAME_DTYPE, LM_OK, lm_batch_result, lm_bb_result, lm_geometry, lm_jpeg_info, lm_jpeg_stats,
+                  result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -37,7 +38,11 @@ HOST_LIB_PATH = os.path.join(PKG, "liblocomouse_host.so")
 CLI_PATH = os.path.join(PKG, "bin", "LocoMouse")
 
 
-HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip")  # translation units of liblocomouse_hip.so
+HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip")  # translation units of liblocomouse_hip.so
+
+# include/locomouse_jpeg.h (device MJPEG decode), same library
+JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
+                 "lm_jpeg_debug_stats", "lm_jpeg_device_alloc", "lm_jpeg_device_free", "lm_jpeg_upload")
 
 
 def _up_to_date(obj, cmd):
@@ -166,6 +171,14 @@ def lib():
         L.lm_host_free.argtypes = [C.c_void_p]
         L.lm_bb_stream.argtypes = [C.c_void_p]
         L.lm_bb_stream.restype = C.c_void_p
+        L.lm_jpeg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lm_jpeg_destroy.argtypes = [C.c_void_p]
+        L.lm_jpeg_decode_device.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32,
+                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+        L.lm_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(lm_jpeg_info)]
+        L.lm_jpeg_stream.argtypes = [C.c_void_p]
+        L.lm_jpeg_stream.restype = C.c_void_p
+        L.lm_jpeg_debug_stats.argtypes = [C.c_void_p, C.POINTER(lm_jpeg_stats)]
         _lib = L
     return _lib
 
@@ -400,6 +413,69 @@ class BBContext:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lm_bb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def jpeg_probe(data):
+    """lm_jpeg_probe: what a JPEG frame is (host only, no GPU call) as a dict;
+    status is abi.LM_JPEG_OK when the device decoder takes it."""
+    info = lm_jpeg_info()
+    _check(lib().lm_jpeg_probe(bytes(data), len(data), C.byref(info)))
+    d = {n: getattr(info, n) for n, _ in lm_jpeg_info._fields_ if n not in ("reserved", "reason")}
+    d["reason"] = info.reason.decode()
+    return d
+
+
+class JpegDecoder:
+    """One lm_jpeg_ctx: JPEG frames of rows x cols decoded on one HIP device
+    from their compressed bytes (include/locomouse_jpeg.h)."""
+
+    def __init__(self, rows, cols, max_batch=64, device=0, subseq_bytes=0):
+        self._h = C.c_void_p()
+        _check(lib().lm_jpeg_create(device, rows, cols, max_batch, subseq_bytes, C.byref(self._h)))
+        self.rows, self.cols, self.max_batch, self.device = rows, cols, max_batch, device
+
+    probe = staticmethod(jpeg_probe)
+
+    def decode_into(self, jpegs, d_out_ptr, pitch=None):
+        """lm_jpeg_decode_device into device memory at d_out_ptr (frame i at
+        d_out_ptr + i * pitch); returns the per-frame statuses (int32 array)."""
+        n = len(jpegs)
+        keep = [bytes(j) for j in jpegs]
+        ptrs = (C.c_char_p * max(n, 1))(*keep)
+        sizes = (C.c_size_t * max(n, 1))(*[len(j) for j in keep])
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().lm_jpeg_decode_device(self._h, ptrs, sizes, n, C.c_void_p(d_out_ptr),
+                                           self.rows * self.cols if pitch is None else pitch,
+                                           status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return status[:n]
+
+    def decode(self, jpegs):
+        """Frames as a torch uint8 tensor [n, rows, cols] on the decoder's
+        device, and the per-frame statuses."""
+        import torch
+        out = torch.empty((max(len(jpegs), 1), self.rows, self.cols), dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(self.device)  # (the decode runs on the context's own stream)
+        status = self.decode_into(jpegs, out.data_ptr())
+        return out[:len(jpegs)], status
+
+    def stats(self):
+        s = lm_jpeg_stats()
+        _check(lib().lm_jpeg_debug_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in lm_jpeg_stats._fields_}
+
+    def stream(self):
+        return lib().lm_jpeg_stream(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().lm_jpeg_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
