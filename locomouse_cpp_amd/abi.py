@@ -174,6 +174,7 @@ BB_FRAME_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y_bottom", "y_side", "widt
 # include/locomouse_jpeg.h (device MJPEG decode)
 LM_JPEG_OK, LM_JPEG_NEEDS_HOST, LM_JPEG_REJECTED = 0, 1, 2
 LM_JPEG_SUBSEQ_MIN, LM_JPEG_SUBSEQ_DEFAULT, LM_JPEG_CHUNK = 4, 64, 128
+LM_BKG_MAX_SAMPLES = 65535  # include/locomouse_bkg.h: frames one lm_bkg_ctx accumulates
 
 
 class lm_jpeg_info(C.Structure):

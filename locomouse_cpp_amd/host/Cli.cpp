@@ -21,9 +21,11 @@
 #include <string>
 #include <vector>
 
+#include "Background.hpp"
 #include "FileStorage.hpp"
 #include "LocoMouse.hpp"
 #include "Media.hpp"
+#include "VideoFrames.hpp"
 
 namespace locomouse {
 namespace {
@@ -97,55 +99,6 @@ ParsedInputs parse_inputs(int argc, char** argv) {
   in.BB_BOTTOM_VIEW = lm_rect{(int)V.v[4], (int)V.v[5], (int)V.v[6], (int)V.v[7]};
   return in;
 }
-
-// V >> F in video order; a whole batch at a time is decoded straight into
-// the caller's batch buffer by worker threads (pread at each frame's offset
-// in the file), so decoding is parallel and costs no extra copy.
-class VideoFrames {
- public:
-  VideoFrames(std::shared_ptr<AviReader> v, int threads)
-      : V(std::move(v)), T(threads), FB((size_t)V->rows() * V->cols()) {}
-  bool read(uint8_t* dst) { return pos < V->frame_count() && V->read_at(pos++, dst); }
-  int read(uint8_t* dst, int n) {
-    const auto t0 = std::chrono::steady_clock::now();
-    n = (int)std::min<size_t>((size_t)std::max(n, 0), V->frame_count() - pos);
-    std::vector<char> ok((size_t)n, 0);
-    std::atomic<int> next{0};
-    auto work = [&] {
-      for (int i; (i = next++) < n;) ok[i] = V->read_at(pos + (size_t)i, dst + (size_t)i * FB) ? 1 : 0;
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < std::min(T, n); ++t) pool.emplace_back(work);
-    work();
-    for (auto& th : pool) th.join();
-    int got = 0;
-    while (got < n && ok[got]) ++got;
-    pos += (size_t)got;
-    decode_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return got;
-  }
-  // The next (up to) n frames' chunks as they are in the file (JPEG images of an MJPEG video), appended to out.
-  int read_compressed(std::vector<std::vector<uint8_t>>& out, int n) {
-    n = (int)std::min<size_t>((size_t)std::max(n, 0), V->frame_count() - pos);
-    int got = 0;
-    for (; got < n; ++got) {
-      std::vector<uint8_t> b;
-      if (!V->read_chunk(pos + (size_t)got, b)) break;
-      out.push_back(std::move(b));
-    }
-    pos += (size_t)got;
-    return got;
-  }
-  int threads() const { return T; }
-  double decode_s = 0;  // wall seconds in read(dst, n): file reads + decoding on T threads
-  void rewind() { pos = 0; }  // V.set(CV_CAP_PROP_POS_FRAMES, 0)
-
- private:
-  std::shared_ptr<AviReader> V;
-  const int T;
-  const size_t FB;
-  size_t pos = 0;
-};
 
 // LocoMouse_Parameters (LocoMouse_class.cpp:4-249): keys in the reference's
 // order, its messages, OpenCV's missing-key-reads-0 semantics.
@@ -302,11 +255,16 @@ int run(int argc, char** argv) {
   li.debug_file = in.OUTPUT_PATH + "/debug_" + in.FILE_STEM + ".yml";  // initializePaths (:361-362)
   li.debug_text = in.OUTPUT_PATH + "/debug_" + in.FILE_STEM + ".txt";
   if (li.n_frames < 1) throw std::invalid_argument("Error: Video has no images to read from.");
+  // LM_BACKGROUND=median[:stride[:permille]] (not in the reference): the background is estimated from the
+  // video (Background.hpp) once the frame reader below exists, and the background argument is not opened
+  BackgroundOptions bkg_opt;
+  const char* bkg_spec = std::getenv("LM_BACKGROUND");
+  if (bkg_spec) parse_background_spec(bkg_spec, bkg_opt);
   int br = 0, bc = 0;
   std::vector<uint8_t> bkg;
-  if (!read_png_gray(in.BKG_FILE, br, bc, bkg))
+  if (!bkg_spec && !read_png_gray(in.BKG_FILE, br, bc, bkg))
     throw std::invalid_argument("Could not open the background image: " + in.BKG_FILE + ".");
-  if (bc != video->cols() || br != video->rows()) {  // validateImageVideoSize (:486-492)
+  if (!bkg_spec && (bc != video->cols() || br != video->rows())) {  // validateImageVideoSize (:486-492)
     std::ostringstream m;
     m << "Error: Background image does not match video size. Background image has size [" << bc << " x " << br
       << "] while Video has size [" << video->cols() << " x " << video->rows() << "]." << '\n';
@@ -373,7 +331,19 @@ int run(int argc, char** argv) {
   if (const char* o = std::getenv("LM_OVERSUBSCRIBE")) li.oversubscribe = std::atoi(o) != 0;
   if (const char* b = std::getenv("LM_BATCH")) li.batch = std::max(1, std::atoi(b));
   if (const char* l = std::getenv("LM_LANES")) li.lanes = std::max(1, std::atoi(l));
-  if (std::getenv("LM_PRINT_INPUTS")) {  // diagnostics: the parsed inputs, nothing run on the GPU
+  double background_ms = 0;
+  if (bkg_spec) {  // before anything else reads the video; the pass rewinds it
+    const auto t0 = std::chrono::steady_clock::now();
+    bkg_opt.device = li.devices.empty() ? li.device : li.devices[0];
+    bkg_opt.batch = li.batch;
+    estimate_background(li, bkg_opt, bkg);
+    li.setup.background = bkg.data();
+    background_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  if (const char* save = std::getenv("LM_BACKGROUND_SAVE"))  // the image in use, estimated or loaded
+    if (!write_png_gray(save, video->rows(), video->cols(), bkg.data()))
+      throw std::runtime_error(std::string("Could not write the background image: ") + save + ".");
+  if (std::getenv("LM_PRINT_INPUTS")) {  // diagnostics: the parsed inputs, nothing run on the GPU (but LM_BACKGROUND's pass above)
     const lm_params& P = li.params;
     std::cout << "method " << method << "\nflip " << li.setup.flip << "\nvideo " << li.setup.video_rows << " "
               << li.setup.video_cols << " " << li.n_frames << "\ncalib " << in.calib_rows << " " << in.calib_cols
@@ -443,7 +413,8 @@ int run(int argc, char** argv) {
               << " decode_ms " << 1e3 * (reader->decode_s - decode_init) << " decode_threads " << reader->threads()
               << " submit_ms " << 1e3 * st.submit_s << " wait_ms " << 1e3 * st.wait_s << " batches " << st.batches
               << " frames " << L->N_frames() << " decode_device_ms " << 1e3 * st.decode_device_s
-              << " decode_fallback_frames " << st.decode_fallback_frames << std::endl;
+              << " decode_fallback_frames " << st.decode_fallback_frames << " background_ms " << background_ms
+              << std::endl;
   }
   return EXIT_SUCCESS;
 }

@@ -97,6 +97,42 @@ bool read_png_gray(const std::string& path, int& rows, int& cols, std::vector<ui
   return true;
 }
 
+bool write_png_gray(const std::string& path, int rows, int cols, const uint8_t* pixels) {
+  if (rows <= 0 || cols <= 0 || !pixels) return false;
+  const size_t stride = (size_t)cols;
+  std::vector<uint8_t> raw((stride + 1) * (size_t)rows);
+  for (int y = 0; y < rows; ++y) {  // filter type 0 (None) on every row
+    raw[(size_t)y * (stride + 1)] = 0;
+    std::memcpy(&raw[(size_t)y * (stride + 1) + 1], pixels + (size_t)y * stride, stride);
+  }
+  uLongf zlen = compressBound((uLong)raw.size());
+  std::vector<uint8_t> z(zlen);
+  if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) != Z_OK) return false;
+  std::vector<uint8_t> out = {137, 80, 78, 71, 13, 10, 26, 10};
+  auto put32 = [&](uint32_t v) {
+    for (int s = 24; s >= 0; s -= 8) out.push_back((uint8_t)(v >> s));
+  };
+  auto chunk = [&](const char* type, const uint8_t* body, size_t len) {
+    put32((uint32_t)len);
+    const size_t at = out.size();
+    out.insert(out.end(), type, type + 4);
+    out.insert(out.end(), body, body + len);
+    put32((uint32_t)crc32(0L, &out[at], (uInt)(4 + len)));
+  };
+  uint8_t ihdr[13] = {0, 0, 0, 0, 0, 0, 0, 0, 8, 0, 0, 0, 0};  // 8-bit grey, deflate, adaptive filtering, no interlace
+  for (int k = 0; k < 4; ++k) {
+    ihdr[k] = (uint8_t)((uint32_t)cols >> (24 - 8 * k));
+    ihdr[4 + k] = (uint8_t)((uint32_t)rows >> (24 - 8 * k));
+  }
+  chunk("IHDR", ihdr, sizeof ihdr);
+  chunk("IDAT", z.data(), (size_t)zlen);
+  chunk("IEND", ihdr, 0);
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) return false;
+  const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+  return std::fclose(f) == 0 && ok;
+}
+
 AviReader::~AviReader() {
   if (f_) std::fclose(f_);
 }

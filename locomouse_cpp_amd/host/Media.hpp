@@ -2,6 +2,7 @@
 // (SURVEY.md §8(f) row 2), native because OpenCV is absent:
 //
 //   read_png_gray  cv::imread(BKG_FILE, CV_LOAD_IMAGE_GRAYSCALE)  (LocoMouse_class.cpp:405-419)
+//   write_png_gray the estimated background (Background.hpp) as a file read_png_gray reads; not in the reference
 //   AviReader      cv::VideoCapture(VIDEO_FILE); V >> F; extractChannel(F, F, 0)
 //                  (:376-403, :1273-1293) for uncompressed AVI (BI_RGB 24-bit
 //                  BGR or 8-bit palettised, and 8-bit 'Y800'/'GREY') and MJPEG
@@ -25,6 +26,11 @@ namespace locomouse {
 // IMREAD_GRAYSCALE; exact byte parity with a given libpng build is unpinned).
 // Returns false when the file cannot be read or decoded (!BKG.data).
 bool read_png_gray(const std::string& path, int& rows, int& cols, std::vector<uint8_t>& pixels);
+
+// rows x cols grey pixels as an 8-bit greyscale PNG: no interlace, filter type
+// 0 on every row, one zlib stream, so read_png_gray and any other PNG reader
+// return the same bytes.  Returns false when the file cannot be written.
+bool write_png_gray(const std::string& path, int rows, int cols, const uint8_t* pixels);
 
 class AviReader {
  public:

@@ -38,11 +38,16 @@ HOST_LIB_PATH = os.path.join(PKG, "liblocomouse_host.so")
 CLI_PATH = os.path.join(PKG, "bin", "LocoMouse")
 
 
-HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip")  # translation units of liblocomouse_hip.so
+HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip")  # translation units of liblocomouse_hip.so
 
 # include/locomouse_jpeg.h (device MJPEG decode), same library
 JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
                  "lm_jpeg_debug_stats", "lm_jpeg_device_alloc", "lm_jpeg_device_free", "lm_jpeg_upload")
+
+# include/locomouse_bkg.h (the background as a per-pixel temporal median), same library
+BKG_EXPORTED = ("lm_bkg_create", "lm_bkg_destroy", "lm_bkg_push", "lm_bkg_push_device", "lm_bkg_finish",
+                "lm_bkg_reset", "lm_bkg_samples", "lm_bkg_stream")
+BKG_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseBackground")
 
 
 def _up_to_date(obj, cmd):
@@ -99,7 +104,8 @@ def build_host(verbose=False):
     """liblocomouse_host.so: the LocoMouse / Candidate / P22D / MyMat C++
     surface (locomouse_cpp_amd/host) linked against the C-ABI library."""
     srcs = [os.path.join(HOST_DIR, f)
-            for f in ("LocoMouse.cpp", "Tracks.cpp", "match2nd.cpp", "FileStorage.cpp", "Media.cpp", "Jpeg.cpp", "Debug.cpp")]
+            for f in ("LocoMouse.cpp", "Tracks.cpp", "match2nd.cpp", "FileStorage.cpp", "Media.cpp", "Jpeg.cpp", "Debug.cpp",
+                      "Background.cpp")]
     flags = ["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
              "-I" + HOST_DIR]
     cmd = [*flags, "-fPIC", "-shared", "-o", HOST_LIB_PATH, *srcs, "-L" + PKG, "-llocomouse_hip", "-lz",
@@ -110,6 +116,12 @@ def build_host(verbose=False):
     # the reference's command-line program (main.cpp), SURVEY.md §8(f) row 2
     os.makedirs(os.path.dirname(CLI_PATH), exist_ok=True)
     cmd = [*flags, "-o", CLI_PATH, os.path.join(HOST_DIR, "Cli.cpp"), "-L" + PKG, "-llocomouse_host",
+           "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # LocoMouseBackground video.avi out.png [stride [permille]]: the background image the program above takes
+    cmd = [*flags, "-o", BKG_CLI_PATH, os.path.join(HOST_DIR, "BackgroundCli.cpp"), "-L" + PKG, "-llocomouse_host",
            "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
     if verbose:
         print(" ".join(cmd))
@@ -179,6 +191,16 @@ def lib():
         L.lm_jpeg_stream.argtypes = [C.c_void_p]
         L.lm_jpeg_stream.restype = C.c_void_p
         L.lm_jpeg_debug_stats.argtypes = [C.c_void_p, C.POINTER(lm_jpeg_stats)]
+        L.lm_bkg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lm_bkg_destroy.argtypes = [C.c_void_p]
+        for fn in (L.lm_bkg_push, L.lm_bkg_push_device):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+        L.lm_bkg_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.lm_bkg_reset.argtypes = [C.c_void_p]
+        L.lm_bkg_samples.argtypes = [C.c_void_p]
+        L.lm_bkg_samples.restype = C.c_int64
+        L.lm_bkg_stream.argtypes = [C.c_void_p]
+        L.lm_bkg_stream.restype = C.c_void_p
         _lib = L
     return _lib
 
@@ -476,6 +498,56 @@ class JpegDecoder:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lm_jpeg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BackgroundEstimator:
+    """One lm_bkg_ctx: the video's background as the per-pixel temporal median
+    (or another rank) of its frames, on one HIP device
+    (include/locomouse_bkg.h).  finish() equals
+    np.sort(stack, axis=0)[(permille * (K - 1)) // 1000] of the K pushed frames."""
+
+    def __init__(self, rows, cols, max_batch=64, device=0):
+        self._h = C.c_void_p()
+        _check(lib().lm_bkg_create(device, rows, cols, max_batch, C.byref(self._h)))
+        self.rows, self.cols, self.max_batch, self.device = rows, cols, max_batch, device
+
+    def push(self, frames):
+        """Host frames [n, rows, cols] u8."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 3 or frames.shape[1:] != (self.rows, self.cols):
+            raise ValueError(f"frames must be [n, {self.rows}, {self.cols}], not {frames.shape}")
+        _check(lib().lm_bkg_push(self._h, frames.ctypes.data, self.rows * self.cols, frames.shape[0]))
+
+    def push_device(self, d_frames_ptr, pitch, n):
+        """Frames in device memory (frame i at d_frames_ptr + i * pitch); they
+        must stay unchanged until the context's stream has passed the push."""
+        _check(lib().lm_bkg_push_device(self._h, C.c_void_p(d_frames_ptr), pitch, n))
+
+    def finish(self, permille=500):
+        out = np.zeros((self.rows, self.cols), dtype=np.uint8)
+        _check(lib().lm_bkg_finish(self._h, permille, out.ctypes.data))
+        return out
+
+    def reset(self):
+        _check(lib().lm_bkg_reset(self._h))
+
+    @property
+    def samples(self):
+        return int(lib().lm_bkg_samples(self._h))
+
+    def stream(self):
+        return lib().lm_bkg_stream(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().lm_bkg_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
