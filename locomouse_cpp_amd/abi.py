@@ -175,6 +175,46 @@ BB_FRAME_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y_bottom", "y_side", "widt
 LM_JPEG_OK, LM_JPEG_NEEDS_HOST, LM_JPEG_REJECTED = 0, 1, 2
 LM_JPEG_SUBSEQ_MIN, LM_JPEG_SUBSEQ_DEFAULT, LM_JPEG_CHUNK = 4, 64, 128
 LM_BKG_MAX_SAMPLES = 65535  # include/locomouse_bkg.h: frames one lm_bkg_ctx accumulates
+# include/locomouse_encode.h
+LM_ENC_GRAY8, LM_ENC_RGB24 = 0, 1
+LM_ENC_BLOCK_WORDS, LM_ENC_MAX_HEADER, LM_ENC_MAX_BLOCKS, LM_ENC_MAX_BATCH, LM_ENC_MAX_RADIUS = 52, 640, 1 << 20, 4096, 64
+LM_ENC_PALETTE = ((255, 0, 0), (0, 255, 0), (0, 128, 255), (255, 255, 0), (255, 0, 255), (0, 255, 255), (255, 128, 0),
+                  (255, 255, 255))
+
+
+class lm_enc_result(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("reserved", C.c_int32),
+        ("data", C.c_void_p),
+        ("offset", C.POINTER(C.c_uint32)),
+        ("size", C.POINTER(C.c_uint32)),
+    ]
+
+
+class lm_enc_stats(C.Structure):
+    _fields_ = [
+        ("bytes_out", C.c_int64),
+        ("device_ms", C.c_double),
+        ("frames", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class lm_enc_mark(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("radius", C.c_int32), ("colour", C.c_int32)]
+
+
+class lm_enc_overlay(C.Structure):
+    _fields_ = [
+        ("cal", C.POINTER(C.c_int32)),
+        ("src_rows", C.c_int32),
+        ("src_cols", C.c_int32),
+        ("calib_rows", C.c_int32),
+        ("calib_cols", C.c_int32),
+        ("flip", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
 
 
 class lm_jpeg_info(C.Structure):

@@ -25,6 +25,7 @@
 #include "FileStorage.hpp"
 #include "LocoMouse.hpp"
 #include "Media.hpp"
+#include "Preview.hpp"
 #include "VideoFrames.hpp"
 
 namespace locomouse {
@@ -260,6 +261,10 @@ int run(int argc, char** argv) {
   BackgroundOptions bkg_opt;
   const char* bkg_spec = std::getenv("LM_BACKGROUND");
   if (bkg_spec) parse_background_spec(bkg_spec, bkg_opt);
+  // LM_PREVIEW=path.avi[:quality[:radius]] (not in the reference): after the results are exported, the annotated
+  // preview video is written there (Preview.hpp)
+  if (const char* pv = std::getenv("LM_PREVIEW"))
+    if (*pv) parse_preview_spec(pv, li.preview);  // set but empty means off, as for LM_DECODE
   int br = 0, bc = 0;
   std::vector<uint8_t> bkg;
   if (!bkg_spec && !read_png_gray(in.BKG_FILE, br, bc, bkg))
@@ -405,15 +410,23 @@ int run(int argc, char** argv) {
   L->computeSideTracks();
   const auto t_tracks = std::chrono::steady_clock::now();
   L->exportResults();
+  const auto t_export = std::chrono::steady_clock::now();
+  const double decode_run = reader->decode_s;  // the reads up to here; the preview pass reads the video once more
+  double preview_ms = 0;
+  if (!li.preview.path.empty()) {  // one more pass over the video, on the first device
+    write_preview(li, L->tracks(), L->N_frames(), video->fps() > 0 ? video->fps() : 30);
+    preview_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_export).count();
+  }
   if (std::getenv("LM_TIMING")) {  // stage times (not in the reference)
     const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const LocoMouse::StageTimes st = L->stage_times();
     std::cout << "LM_TIMING init_ms " << ms(t_start, t_init) << " loop_ms " << ms(t_init, t_loop) << " tracks_ms "
-              << ms(t_loop, t_tracks) << " export_ms " << ms(t_tracks, std::chrono::steady_clock::now())
-              << " decode_ms " << 1e3 * (reader->decode_s - decode_init) << " decode_threads " << reader->threads()
+              << ms(t_loop, t_tracks) << " export_ms " << ms(t_tracks, t_export)
+              << " decode_ms " << 1e3 * (decode_run - decode_init) << " decode_threads " << reader->threads()
               << " submit_ms " << 1e3 * st.submit_s << " wait_ms " << 1e3 * st.wait_s << " batches " << st.batches
               << " frames " << L->N_frames() << " decode_device_ms " << 1e3 * st.decode_device_s
               << " decode_fallback_frames " << st.decode_fallback_frames << " background_ms " << background_ms
+              << " preview_ms " << preview_ms << " preview_decode_ms " << 1e3 * (reader->decode_s - decode_run)
               << std::endl;
   }
   return EXIT_SUCCESS;

@@ -104,6 +104,14 @@ struct LocoMouse_Inputs {
   // <outdir>/debug_<stem>.txt / .yml (:361-362).  Empty paths: not written.
   bool verbose_debug = false;
   std::string debug_file, debug_text;
+  // The annotated preview video (Preview.hpp; not in the reference): after
+  // exportResults, every frame as the detector's geometry sees it with the
+  // exported tracks drawn on it, as an MJPEG AVI at `path`.  Empty: none.
+  struct Preview {
+    std::string path;
+    int quality = 90;  // JPEG quality, 1..100
+    int radius = 3;    // half side of a paw's or the snout's mark (a tail point's is 1)
+  } preview;
 };
 
 class LocoMouse : protected FrameResults {

@@ -143,6 +143,7 @@ bool AviReader::open(const std::string& path) {
   if (!f_) return false;
   frames_.clear();
   next_ = 0;
+  fps_ = 0;
   uint8_t hdr[12];
   if (std::fread(hdr, 1, 12, f_) != 12 || std::memcmp(hdr, "RIFF", 4) || std::memcmp(hdr + 8, "AVI ", 4)) return false;
   std::fseek(f_, 0, SEEK_END);
@@ -185,7 +186,11 @@ bool AviReader::open(const std::string& path) {
     if (!b.empty() && std::fread(b.data(), 1, b.size(), f_) != b.size()) return false;
     if (!std::memcmp(ck, "strh", 4) && b.size() >= 8) {
       ++stream_index;
-      if (!std::memcmp(b.data(), "vids", 4) && video_stream < 0) video_stream = stream_index;
+      if (!std::memcmp(b.data(), "vids", 4) && video_stream < 0) {
+        video_stream = stream_index;
+        const uint64_t scale = b.size() >= 28 ? le32(&b[20]) : 0, rate = b.size() >= 28 ? le32(&b[24]) : 0;
+        if (scale > 0) fps_ = (int)std::min<uint64_t>((rate + scale / 2) / scale, 1000000);  // dwRate / dwScale, rounded
+      }
     } else if (!std::memcmp(ck, "strf", 4) && stream_index == video_stream && video_stream >= 0 && !have_format &&
                b.size() >= 40) {
       width_ = (int)le32(&b[4]);
@@ -282,6 +287,123 @@ bool AviReader::read_at(size_t index, uint8_t* channel0) const {
     }
   }
   return true;
+}
+
+// ---- MjpegAviWriter
+namespace {
+
+void put32(std::vector<uint8_t>& b, uint32_t v) {
+  for (int i = 0; i < 4; ++i) b.push_back((uint8_t)(v >> (8 * i)));
+}
+void put16(std::vector<uint8_t>& b, uint32_t v) {
+  b.push_back((uint8_t)v);
+  b.push_back((uint8_t)(v >> 8));
+}
+void put_tag(std::vector<uint8_t>& b, const char* t) { b.insert(b.end(), t, t + 4); }
+
+constexpr uint32_t kAviHeaderBytes = 224;  // RIFF .. the 'movi' tag: the chunks start here
+
+// RIFF / hdrl (avih, strl: strh + strf) / the head of the movi list.
+std::vector<uint8_t> avi_header(int w, int h, int fps, uint32_t n, uint32_t largest, uint64_t movi_bytes, uint64_t idx_bytes) {
+  std::vector<uint8_t> b;
+  put_tag(b, "RIFF");
+  put32(b, (uint32_t)(kAviHeaderBytes - 12 + movi_bytes + idx_bytes));
+  put_tag(b, "AVI ");
+  put_tag(b, "LIST");
+  put32(b, 192);
+  put_tag(b, "hdrl");
+  put_tag(b, "avih");
+  put32(b, 56);
+  for (uint32_t v : {1000000u / (uint32_t)fps, 0u, 0u, 0x10u /* AVIF_HASINDEX */, n, 0u, 1u, largest, (uint32_t)w, (uint32_t)h,
+                     0u, 0u, 0u, 0u})
+    put32(b, v);
+  put_tag(b, "LIST");
+  put32(b, 116);
+  put_tag(b, "strl");
+  put_tag(b, "strh");
+  put32(b, 56);
+  put_tag(b, "vids");
+  put_tag(b, "MJPG");
+  put32(b, 0);  // flags
+  put16(b, 0);  // priority
+  put16(b, 0);  // language
+  for (uint32_t v : {0u, 1u /* scale */, (uint32_t)fps /* rate */, 0u, n, largest, 0xFFFFFFFFu, 0u}) put32(b, v);
+  for (uint32_t v : {0u, 0u, (uint32_t)w, (uint32_t)h}) put16(b, v);
+  put_tag(b, "strf");
+  put32(b, 40);
+  put32(b, 40);
+  put32(b, (uint32_t)w);
+  put32(b, (uint32_t)h);
+  put16(b, 1);
+  put16(b, 24);
+  put_tag(b, "MJPG");
+  put32(b, (uint32_t)w * (uint32_t)h * 3u);
+  for (int i = 0; i < 4; ++i) put32(b, 0);
+  put_tag(b, "LIST");
+  put32(b, (uint32_t)movi_bytes);
+  put_tag(b, "movi");
+  return b;
+}
+
+}  // namespace
+
+MjpegAviWriter::~MjpegAviWriter() {
+  if (f_) close();
+}
+
+bool MjpegAviWriter::open(const std::string& path, int rows, int cols, int fps) {
+  if (f_) close();
+  if (rows < 1 || cols < 1 || fps < 1) return false;
+  f_ = std::fopen(path.c_str(), "wb");
+  if (!f_) return false;
+  width_ = cols;
+  height_ = rows;
+  fps_ = fps;
+  ok_ = true;
+  movi_bytes_ = 4;
+  largest_ = 0;
+  index_.clear();
+  const std::vector<uint8_t> h = avi_header(width_, height_, fps_, 0, 0, movi_bytes_, 0);
+  ok_ = h.size() == kAviHeaderBytes && std::fwrite(h.data(), 1, h.size(), f_) == h.size();
+  return ok_;
+}
+
+bool MjpegAviWriter::fits(size_t size) const {
+  // headers + movi + this chunk + the index with its entry
+  const uint64_t padded = (uint64_t)size + (size & 1);
+  return (uint64_t)kAviHeaderBytes + movi_bytes_ + 8 + padded + 8 + 16 * (uint64_t)(index_.size() + 1) <= 0xFFFFFFF0ull;
+}
+
+bool MjpegAviWriter::add(const uint8_t* jpeg, size_t size) {
+  if (!f_ || !ok_ || !jpeg) return false;
+  const uint64_t padded = (uint64_t)size + (size & 1);
+  if (!fits(size)) return ok_ = false;
+  uint8_t ck[8] = {'0', '0', 'd', 'c', (uint8_t)size, (uint8_t)(size >> 8), (uint8_t)(size >> 16), (uint8_t)(size >> 24)};
+  ok_ = std::fwrite(ck, 1, 8, f_) == 8 && std::fwrite(jpeg, 1, size, f_) == size;
+  if (ok_ && (size & 1)) ok_ = std::fputc(0, f_) != EOF;
+  index_.emplace_back((uint32_t)movi_bytes_, (uint32_t)size);
+  movi_bytes_ += 8 + padded;
+  largest_ = std::max(largest_, (uint32_t)size);
+  return ok_;
+}
+
+bool MjpegAviWriter::close() {
+  if (!f_) return false;
+  std::vector<uint8_t> idx;
+  put_tag(idx, "idx1");
+  put32(idx, (uint32_t)(16 * index_.size()));
+  for (const auto& e : index_) {
+    put_tag(idx, "00dc");
+    put32(idx, 0x10);  // AVIIF_KEYFRAME
+    put32(idx, e.first);
+    put32(idx, e.second);
+  }
+  ok_ = ok_ && std::fwrite(idx.data(), 1, idx.size(), f_) == idx.size();
+  const std::vector<uint8_t> h = avi_header(width_, height_, fps_, (uint32_t)index_.size(), largest_, movi_bytes_, idx.size());
+  ok_ = ok_ && std::fseek(f_, 0, SEEK_SET) == 0 && std::fwrite(h.data(), 1, h.size(), f_) == h.size();
+  ok_ = (std::fclose(f_) == 0) && ok_;
+  f_ = nullptr;
+  return ok_;
 }
 
 }  // namespace locomouse

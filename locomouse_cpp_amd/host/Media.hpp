@@ -10,6 +10,9 @@
 //                  frame, Jpeg.hpp); channel 0 of the decoded BGR frame is
 //                  blue.  Other codecs (H.264 …) are not decoded: opening
 //                  such a file fails like a VideoCapture that cannot open it.
+//   MjpegAviWriter the annotated preview video (LM_PREVIEW): an
+//                  MJPG AVI that AviReader and ordinary players open; not in
+//                  the reference
 #ifndef LOCOMOUSE_HOST_MEDIA_HPP
 #define LOCOMOUSE_HOST_MEDIA_HPP
 
@@ -50,6 +53,8 @@ class AviReader {
   bool read_at(size_t index, uint8_t* channel0) const;
   // MJPEG ('MJPG'/'JPEG'/'AVI1'): every frame chunk is one JPEG image.
   bool is_mjpeg() const { return mjpeg_; }
+  // Frames per second of the video stream (dwRate / dwScale of its 'strh', rounded), 0 when the file does not say.
+  int fps() const { return fps_; }
   // The raw bytes of frame `index`'s chunk (a JPEG image when is_mjpeg()),
   // without moving the read position; thread-safe like read_at.
   bool read_chunk(size_t index, std::vector<uint8_t>& bytes) const;
@@ -59,9 +64,37 @@ class AviReader {
   int width_ = 0, height_ = 0, bits_ = 0;
   bool bottom_up_ = true;
   bool mjpeg_ = false;
+  int fps_ = 0;
   std::vector<uint8_t> palette_blue_;  // 8-bit palettised: blue of each entry
   std::vector<std::pair<long, uint32_t>> frames_;  // (file offset, size) of each frame chunk
   size_t next_ = 0;
+};
+
+// MJPEG AVI: one JPEG image per '00dc' chunk of the 'movi' list, an 'idx1'
+// index behind it, and the 'avih' / 'strh' / 'strf' fields AviReader reads back
+// (compression 'MJPG', 24 bits, cols x rows).  Frames are appended as they
+// come; close() writes the index and the counts into the headers.
+class MjpegAviWriter {
+ public:
+  MjpegAviWriter() = default;
+  ~MjpegAviWriter();
+  MjpegAviWriter(const MjpegAviWriter&) = delete;
+  MjpegAviWriter& operator=(const MjpegAviWriter&) = delete;
+
+  bool open(const std::string& path, int rows, int cols, int fps);  // fps >= 1
+  bool add(const uint8_t* jpeg, size_t size);  // false: not open, write error, or the file would pass 4 GiB
+  // Whether a frame of `size` bytes still fits: RIFF sizes are 32 bits, so headers, frames and index stay below 4 GiB.
+  bool fits(size_t size) const;
+  bool close();                                // false when anything could not be written
+  uint32_t frame_count() const { return (uint32_t)index_.size(); }
+
+ private:
+  std::FILE* f_ = nullptr;
+  int width_ = 0, height_ = 0, fps_ = 30;
+  bool ok_ = true;
+  uint64_t movi_bytes_ = 4;  // 'movi' + the chunks
+  uint32_t largest_ = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> index_;  // (offset from 'movi', size) of each chunk
 };
 
 }  // namespace locomouse

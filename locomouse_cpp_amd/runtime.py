@@ -10,8 +10,8 @@ import subprocess
 
 import numpy as np
 
-from .abi import (BB_FRAME_DTYPE, LM_OK, lm_batch_result, lm_bb_result, lm_geometry, lm_jpeg_info, lm_jpeg_stats,
-                  result_to_numpy)
+from .abi import (BB_FRAME_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result, lm_enc_mark,
+                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_stats, result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -38,7 +38,8 @@ HOST_LIB_PATH = os.path.join(PKG, "liblocomouse_host.so")
 CLI_PATH = os.path.join(PKG, "bin", "LocoMouse")
 
 
-HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip")  # translation units of liblocomouse_hip.so
+# translation units of liblocomouse_hip.so
+HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip", "lm_jpeg_enc.hip")
 
 # include/locomouse_jpeg.h (device MJPEG decode), same library
 JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
@@ -48,6 +49,11 @@ JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "
 BKG_EXPORTED = ("lm_bkg_create", "lm_bkg_destroy", "lm_bkg_push", "lm_bkg_push_device", "lm_bkg_finish",
                 "lm_bkg_reset", "lm_bkg_samples", "lm_bkg_stream")
 BKG_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseBackground")
+
+# include/locomouse_encode.h (device JPEG encode and the track overlay), same library
+ENC_EXPORTED = ("lm_enc_slot_bytes", "lm_enc_create", "lm_enc_destroy", "lm_enc_encode_device", "lm_enc_encode",
+                "lm_enc_set_overlay", "lm_enc_render_encode_device", "lm_enc_render_encode", "lm_enc_render_device", "lm_enc_stream",
+                "lm_enc_last_stats")
 
 
 def _up_to_date(obj, cmd):
@@ -105,7 +111,7 @@ def build_host(verbose=False):
     surface (locomouse_cpp_amd/host) linked against the C-ABI library."""
     srcs = [os.path.join(HOST_DIR, f)
             for f in ("LocoMouse.cpp", "Tracks.cpp", "match2nd.cpp", "FileStorage.cpp", "Media.cpp", "Jpeg.cpp", "Debug.cpp",
-                      "Background.cpp")]
+                      "Background.cpp", "JpegEncode.cpp", "Preview.cpp")]
     flags = ["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
              "-I" + HOST_DIR]
     cmd = [*flags, "-fPIC", "-shared", "-o", HOST_LIB_PATH, *srcs, "-L" + PKG, "-llocomouse_hip", "-lz",
@@ -201,6 +207,19 @@ def lib():
         L.lm_bkg_samples.restype = C.c_int64
         L.lm_bkg_stream.argtypes = [C.c_void_p]
         L.lm_bkg_stream.restype = C.c_void_p
+        L.lm_enc_slot_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lm_enc_slot_bytes.restype = C.c_int64
+        L.lm_enc_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lm_enc_destroy.argtypes = [C.c_void_p]
+        for fn in (L.lm_enc_encode_device, L.lm_enc_encode):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(lm_enc_result)]
+        L.lm_enc_set_overlay.argtypes = [C.c_void_p, C.POINTER(lm_enc_overlay)]
+        for fn in (L.lm_enc_render_encode_device, L.lm_enc_render_encode):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(lm_enc_result)]
+        L.lm_enc_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lm_enc_stream.argtypes = [C.c_void_p]
+        L.lm_enc_stream.restype = C.c_void_p
+        L.lm_enc_last_stats.argtypes = [C.c_void_p, C.POINTER(lm_enc_stats)]
         _lib = L
     return _lib
 
@@ -548,6 +567,114 @@ class BackgroundEstimator:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lm_bkg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JpegEncoder:
+    """One lm_enc_ctx: frames of rows x cols (LM_ENC_GRAY8, or LM_ENC_RGB24 as
+    YCbCr 4:2:0) encoded as baseline JPEG files on one HIP device, byte for
+    byte the host encoder's and libjpeg's (include/locomouse_encode.h); with
+    set_overlay(), raw frames rendered through the calibration map with marks
+    drawn on them first."""
+
+    GRAY8, RGB24 = LM_ENC_GRAY8, LM_ENC_RGB24
+
+    def __init__(self, rows, cols, fmt=LM_ENC_GRAY8, quality=90, max_batch=64, device=0):
+        self._h = C.c_void_p()
+        _check(lib().lm_enc_create(device, rows, cols, fmt, quality, max_batch, C.byref(self._h)))
+        self.rows, self.cols, self.fmt, self.quality = rows, cols, fmt, quality
+        self.max_batch, self.device = max_batch, device
+        self.frame_bytes = rows * cols * (3 if fmt == LM_ENC_RGB24 else 1)
+        self._src = None
+
+    @staticmethod
+    def slot_bytes(rows, cols, fmt):
+        return int(lib().lm_enc_slot_bytes(rows, cols, fmt))
+
+    @staticmethod
+    def _files(res):
+        n = res.n
+        total = res.offset[n - 1] + res.size[n - 1]
+        data = C.string_at(res.data, total)
+        return [data[res.offset[i]:res.offset[i] + res.size[i]] for i in range(n)]
+
+    def encode(self, frames):
+        """Host frames [n, rows, cols] (grey) or [n, rows, cols, 3] (RGB) u8 -> the n JPEG files (bytes)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        want = (self.rows, self.cols) if self.fmt == LM_ENC_GRAY8 else (self.rows, self.cols, 3)
+        if frames.shape[1:] != want:
+            raise ValueError(f"frames must be [n, {', '.join(map(str, want))}], not {frames.shape}")
+        res = lm_enc_result()
+        _check(lib().lm_enc_encode(self._h, frames.ctypes.data, self.frame_bytes, frames.shape[0], C.byref(res)))
+        return self._files(res)
+
+    def encode_device(self, d_frames_ptr, n, pitch=None, files=True):
+        """Frames in device memory (frame i at d_frames_ptr + i * pitch)."""
+        res = lm_enc_result()
+        _check(lib().lm_enc_encode_device(self._h, C.c_void_p(d_frames_ptr), self.frame_bytes if pitch is None else pitch, n,
+                                          C.byref(res)))
+        return self._files(res) if files else None
+
+    def set_overlay(self, cal, src_rows, src_cols, flip):
+        """The canvas geometry: cal [rows, cols] int32 indices into a raw src_rows x src_cols frame."""
+        self._cal = np.ascontiguousarray(cal, dtype=np.int32)
+        geo = lm_enc_overlay(C.cast(self._cal.ctypes.data, C.POINTER(C.c_int32)), src_rows, src_cols, self._cal.shape[0],
+                             self._cal.shape[1], int(bool(flip)), 0)
+        _check(lib().lm_enc_set_overlay(self._h, C.byref(geo)))
+        self._src = (src_rows, src_cols)
+
+    @staticmethod
+    def _marks(marks_per_frame):
+        flat = [m for per in marks_per_frame for m in per]
+        arr = (lm_enc_mark * max(len(flat), 1))(*[lm_enc_mark(*map(int, m)) for m in flat])
+        off = np.zeros(len(marks_per_frame) + 1, np.int32)
+        off[1:] = np.cumsum([len(per) for per in marks_per_frame])
+        return arr, off
+
+    def render_encode_device(self, d_raw_ptr, pitch, marks_per_frame, files=True):
+        """Raw frames in device memory rendered with each frame's marks [(x, y, radius, colour), ...] and encoded."""
+        arr, off = self._marks(marks_per_frame)
+        res = lm_enc_result()
+        _check(lib().lm_enc_render_encode_device(self._h, C.c_void_p(d_raw_ptr), pitch, len(marks_per_frame), arr,
+                                                 off.ctypes.data, C.byref(res)))
+        return self._files(res) if files else None
+
+    def render_encode(self, raw, marks_per_frame):
+        """The same for host frames [n, src_rows, src_cols] u8, uploaded first."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        if raw.shape != (len(marks_per_frame), *self._src):
+            raise ValueError(f"raw must be [{len(marks_per_frame)}, {self._src[0]}, {self._src[1]}], not {raw.shape}")
+        arr, off = self._marks(marks_per_frame)
+        res = lm_enc_result()
+        _check(lib().lm_enc_render_encode(self._h, raw.ctypes.data, raw.shape[1] * raw.shape[2], raw.shape[0], arr,
+                                          off.ctypes.data, C.byref(res)))
+        return self._files(res)
+
+    def render_device(self, d_raw_ptr, pitch, marks_per_frame):
+        """The rendered canvases [n, rows, cols, 3] u8 (test access)."""
+        arr, off = self._marks(marks_per_frame)
+        out = np.zeros((len(marks_per_frame), self.rows, self.cols, 3), np.uint8)
+        _check(lib().lm_enc_render_device(self._h, C.c_void_p(d_raw_ptr), pitch, len(marks_per_frame), arr, off.ctypes.data,
+                                          out.ctypes.data))
+        return out
+
+    def stats(self):
+        s = lm_enc_stats()
+        _check(lib().lm_enc_last_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in lm_enc_stats._fields_ if n != "reserved"}
+
+    def stream(self):
+        return lib().lm_enc_stream(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().lm_enc_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -30,6 +30,12 @@ in turn on the same video, REPS times each, every repetition recorded; the
 host runs are the baseline.
 
   python scripts/cli_e2e_mjpeg.py --decode host,device --reps 3 --out profiles/r07/e2e/e2e_decode.json
+
+With --preview the runs are one device without and with LM_PREVIEW (the
+annotated preview video) in turn on the same video, REPS times
+each, every repetition recorded; the runs without it are the baseline.
+
+  python scripts/cli_e2e_mjpeg.py --preview --reps 3 --out profiles/r09/preview/e2e.json
 """
 import argparse
 import json
@@ -118,6 +124,8 @@ def main():
     ap.add_argument("--decode", default=None,
                     help="comma-separated LM_DECODE choices (host,device): one device, the choices run in turn "
                          "within each repetition on the same video, every repetition recorded")
+    ap.add_argument("--preview", action="store_true",
+                    help="one device, without and with LM_PREVIEW in turn within each repetition, every repetition recorded")
     a = ap.parse_args()
     from oracle import oracle as O
     cfg = S.SyntheticConfig()
@@ -151,8 +159,13 @@ def main():
         if a.decode:
             modes = {f"decode {c}": {"LM_DECODE": c} for c in a.decode.split(",") if c}
             tag = {m: e["LM_DECODE"] for m, e in modes.items()}
-        # with --decode the choices alternate (host, device, host, ...), so drift hits both alike
-        order = [m for _ in range(a.reps) for m in modes] if a.decode else [m for m in modes for _ in range(a.reps)]
+        if a.preview:
+            preview = os.path.join(d, "preview.avi")
+            modes = {"no preview": {}, "preview": {"LM_PREVIEW": preview}}
+            tag = {"no preview": "plain", "preview": "preview"}
+        alternate = bool(a.decode or a.preview)
+        # with --decode / --preview the choices alternate (host, device, host, ...), so drift hits both alike
+        order = [m for _ in range(a.reps) for m in modes] if alternate else [m for m in modes for _ in range(a.reps)]
         reps = {m: [] for m in modes}
         for name in order:
             t0 = time.perf_counter()
@@ -169,13 +182,17 @@ def main():
                 r["decode_frames_per_s"] = round(n / (st["decode_ms"] / 1e3), 1)
             if st.get("decode_device_ms"):
                 r["decode_device_frames_per_s"] = round(n / (st["decode_device_ms"] / 1e3), 1)
+            if st.get("preview_ms"):
+                r["preview_frames_per_s"] = round(n / (st["preview_ms"] / 1e3), 1)
+                r["preview_bytes"] = os.path.getsize(modes[name]["LM_PREVIEW"])
             reps[name].append(r)
             if len(reps[name]) == a.reps:  # the mode's last run: keep its YAML for the tracks check
                 os.rename(yml, yml + "." + tag[name])
         runs = {}
         for name, env in modes.items():  # the fastest repetition's figures, as before; with --decode all of them too
-            runs[name] = dict(min(reps[name], key=lambda r: r["wall_s"]), env=env)
-            if a.decode:
+            shown = {k: (os.path.basename(v) if k == "LM_PREVIEW" else v) for k, v in env.items()}
+            runs[name] = dict(min(reps[name], key=lambda r: r["wall_s"]), env=shown)
+            if alternate:
                 runs[name]["reps"] = reps[name]
         out["runs"] = runs
         if not a.no_check:
