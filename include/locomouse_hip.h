@@ -346,6 +346,23 @@ int32_t lm_debug_kernel_spans(lm_ctx* ctx, const char** names, double* t0, doubl
  * are not computed.  -1 when not recorded (timing off, LM_CORR_DARK=0). */
 lm_status lm_debug_corr_work(const lm_ctx* ctx, int32_t* out);
 
+/* Tail-detector work of the last collected batch.  The pipeline uses only the
+ * sign of a tail score (threshold(> 0), LocoMouse_class.cpp:2593), so a tile
+ * of the dark-tile grid whose scores a bound from the tile's pixel ranges
+ * proves < 0 in the kernels' own fp32 arithmetic is not computed
+ * (LM_CORR_TAILSKIP=0 in the environment at lm_ctx_create: compute every
+ * tile).  out[0], out[1] = tiles listed for computing and all tiles of
+ * tail_bottom over the batch's slots, out[2], out[3] = of tail_side; -1 with
+ * the skip off (and in the LM_CORR_F16 mode).  Like lm_debug_scores this
+ * reads the lane the batch ran on and fails once that lane was reused. */
+lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out);
+
+/* The flag bytes behind those counts for frame f of the last collected batch:
+ * out[ty * cols + tx] = 1 when tile (ty, tx) of tail detector `view`
+ * (0 bottom, 1 side) was listed; rows x cols = ceil(oh / tile height) x
+ * ceil(ow / tile width) of its outputs. */
+lm_status lm_debug_tail_tiles(lm_ctx* ctx, int32_t f, int32_t view, uint8_t* out, int32_t rows, int32_t cols);
+
 /* The dark-tile grid: tiles of lm_debug_dark_tile_width() x
  * lm_debug_dark_tile_height() outputs (40 x 4 in the default build; 40 x 8
  * and 80 x 8 as build options, -DLM_FH=8 / -DLM_FW=80). */

@@ -126,16 +126,24 @@ const void* corr_kernel_f16(int kw);           // nullptr when kw is too wide
 // Dark tiles of a batch (written by k_ingest, lm_kernels.hip): flag bytes
 // per (slot, view, tile), the bright tiles' list per view and their counts.
 // All null: every tile is computed (LM_CORR_DARK=0).
+// tail_*: the same for the tail detectors' tiles that are not proven
+// non-positive (written by k_tail_bound); all null: every tail tile is
+// computed (LM_CORR_TAILSKIP=0, the f16 mode).
 struct CorrDark {
   uint8_t* flags = nullptr;
   int32_t* cnt = nullptr;
   uint32_t* list = nullptr;
+  uint8_t* tail_flags = nullptr;
+  int32_t* tail_cnt = nullptr;
+  uint32_t* tail_list = nullptr;
 };
 // Launch the correlation for one detector group (`weights`: the fp32 rows, or
 // the f16 B fragments for k_corr_f16).  Ring kernels take one wave per tile
 // with the batch's tiles flattened (grid.y = slot count; with dark-tile lists
-// the point detectors' waves are their bright tiles only); the others one
-// workgroup per (tile, slot), dark workgroups returning at once.
+// the point detectors' waves are their bright tiles only, with tail-tile
+// lists the tail detectors' waves the listed tiles only); the others one
+// workgroup per (tile, slot), dark workgroups and k_corr_gen's workgroups
+// without a listed tail tile returning at once.
 hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t lds, hipStream_t st, const LmConst* K,
                        const LmDetGroup& G, const uint8_t* ext, int64_t ext_slot_bytes, const void* weights, int s0,
                        unsigned long long* keys, int32_t* n_pos, uint8_t* tailbin, int64_t tailbin_slot_bytes,

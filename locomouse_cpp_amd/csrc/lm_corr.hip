@@ -203,17 +203,15 @@ DEV const uint8_t* corr_src(const LmConst& K, const LmDet& D, const uint8_t* ext
 // one column: for tap (i, j) both use weight w[i][j] (SGPR, broadcast) and
 // pixels (t, t+1) of one column, which one ds_read2_b32 loads into an aligned
 // register pair.  A thread owns 5 columns x 4 rows (two row pairs sharing the
-// pixel rows of a step with weight rows t and t - 2).  A wave is LM_RW_NQ
-// independent sub-tiles of LM_FW x 8 outputs (round 4: four 40 x 8 quarters
-// of 16 lanes, 8 x 2 threads; round 3: two 80 x 8 halves of 32 lanes), so
-// the dark-tile skip works at LM_FW x 8 granularity (60-62 % of the
-// synthetic point outputs in bright 40 x 8 tiles vs 72-73 % at 80 x 8), each
-// streaming its own window through a private LDS ring of LM_RW_HSLOTS rows +
-// 1 mirror row: at step t its 2 row groups read window rows t + 4 ly,
-// t + 4 ly + 1 (rows t .. t + 5), the ring also holds the rows loaded ahead,
-// and the mirror slot keeps a pair from wrapping.  Any kh fits, no wave waits
-// for another and a wave's LDS operations execute in order, so the rings need
-// no barrier.
+// pixel rows of a step with weight rows t and t - 2).  A wave is LM_RW_NQ = 8
+// independent sub-tiles of LM_FW x LM_FH = 40 x 4 outputs, one row of 8 lanes
+// each (rw_tile), so the dark-tile skip of the point detectors and the
+// proven-tile skip of the tail detectors work at 40 x 4 granularity.  Each
+// sub-tile streams its own window (kh + 3 rows) through a private LDS ring of
+// LM_RW_HSLOTS = 3 rows + 1 mirror row: at step t its lanes read window rows
+// t and t + 1, the third slot holds the row loaded ahead, and the mirror slot
+// keeps a pair from wrapping.  Any kh fits, no wave waits for another and a
+// wave's LDS operations execute in order, so the rings need no barrier.
 
 // A ring wave's work (see rw_tile): LM_RW_NQ sub-tiles of LM_FW x LM_FH
 // outputs -- LM_RW_NQ bright tiles from a segment of a dark-tile list (the
@@ -247,10 +245,16 @@ struct RwRun {
 // detector's waves take its view's bright LM_FW x LM_FH tiles LM_RW_NQ at a
 // time from the list segments k_ingest filled (segment c: tl_cnt[view
 // LM_TL_NC + c] tiles, ceil(/ LM_RW_NQ) waves), packed densely: a wave finds
-// its segment with one scan over the 64 counters, one per lane.  The group's
-// wave count is known on the device only, so the grid is sized for every
-// 80 x 16 tile and the waves past the last group's count (whole workgroups
-// at the grid's end) return.  Otherwise a wave takes the sub-tiles of one
+// its segment with one scan over the 64 counters, one per lane.  With
+// tail-tile lists (tt_cnt != nullptr) a tail detector's waves take the tiles
+// k_tail_bound could not prove non-positive from its segments in the same
+// way.  The group's wave count is known on the device only, so the grid is
+// sized for every 80 x 16 tile and the waves past the last group's count
+// (whole workgroups at the grid's end) return.  That is enough: a segment
+// holds the tiles of whole slots, a slot lists at most the 8 sub-tile places
+// of each of its nt 80 x 16 tiles (edge tiles fewer), so a segment of k slots
+// needs at most ceil(8 nt k / 8) = nt k waves, and the segments' slots add
+// up to the batch's.  Otherwise a wave takes the sub-tiles of one
 // 80 x 16 tile (row-major per slot).  Called by every lane of the wave;
 // false: past the last wave.
 //
@@ -263,7 +267,7 @@ struct RwRun {
 // between the working ones; the dense layout has neither.
 static_assert(LM_TL_NC == 64, "one list counter per lane");
 DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
-                        const uint32_t* tl_list, int& d, RwRun& R) {
+                        const uint32_t* tl_list, const int32_t* tt_cnt, const uint32_t* tt_list, int& d, RwRun& R) {
   constexpr int NQ = LM_RW_NQ;
   const int lane = threadIdx.x & 63;
   int base = 0;
@@ -273,9 +277,12 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
     const int dk = G.ids[k];
     const LmDet& D = K.det[dk];
     const int nt = G.tile_end[k] - (k ? G.tile_end[k - 1] : 0);
-    if (tl_cnt != nullptr && D.kind == 0) {
-      const int v = D.view;
-      const int cn = tl_cnt[v * LM_TL_NC + lane];  // segment `lane`'s bright tiles
+    const bool pt = tl_cnt != nullptr && D.kind == 0;  // bright tiles of the view
+    if (pt || (tt_cnt != nullptr && D.kind != 0)) {    // or the tail detector's tiles that are not proven
+      const int v = pt ? D.view : D.list;
+      const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], ntile = ftx * (pt ? K.fl_ty[v] : K.tt_ty[v]);
+      const uint32_t* lst = pt ? tl_list + (int64_t)v * K.tl_stride : tt_list + (int64_t)v * K.tt_stride;
+      const int cn = (pt ? tl_cnt : tt_cnt)[v * LM_TL_NC + lane];  // segment `lane`'s tiles
       const int wv = (cn + NQ - 1) / NQ;
       int P = wv;  // inclusive scan: waves of segments 0 .. lane
 #pragma unroll
@@ -290,9 +297,8 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
         const int w = local - (__builtin_amdgcn_readlane(P, c) - __builtin_amdgcn_readlane(wv, c));  // place in segment c
         const int ng = (nslots + LM_INGEST_FB - 1) / LM_INGEST_FB;
         d = dk;
-        R = RwRun{tl_list + (int64_t)v * K.tl_stride + (int64_t)lm_tl_y0(c, ng) * LM_INGEST_FB * K.fl_tx[v] * K.fl_ty[v] +
-                      NQ * w,
-                  min(NQ, __builtin_amdgcn_readlane(cn, c) - NQ * w), K.fl_tx[v], 0, 0, 0};
+        R = RwRun{lst + (int64_t)lm_tl_y0(c, ng) * LM_INGEST_FB * ntile + NQ * w,
+                  min(NQ, __builtin_amdgcn_readlane(cn, c) - NQ * w), ftx, 0, 0, 0};
         return true;
       }
       base += cnt;
@@ -314,15 +320,21 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
 
 // A workgroup tile of a point detector (k_corr_gen, k_corr_f16) whose flag
 // tiles are all dark has no output that survives the mask.
-DEV bool corr_tile_dark(const LmConst& K, const LmDet& D, const uint8_t* __restrict__ dark, int slot, int oy0, int ox0) {
-  if (dark == nullptr || D.kind != 0) return false;
-  const int v = D.view;
-  const int ty0 = oy0 / LM_FH, ty1 = min(K.fl_ty[v] - 1, (oy0 + D.tile_h - 1) / LM_FH);
-  const int tx0 = ox0 / LM_FW, tx1 = min(K.fl_tx[v] - 1, (ox0 + D.tile_w - 1) / LM_FW);
-  const uint8_t* __restrict__ f = dark + (int64_t)slot * K.fl_slot + K.fl_off[v];
+// The same for a tail detector (k_corr_gen) and the tiles k_tail_bound has
+// proven non-positive (flag 0): none of its outputs sets a bit.
+DEV bool corr_tile_dark(const LmConst& K, const LmDet& D, const uint8_t* __restrict__ dark,
+                        const uint8_t* __restrict__ tail_flags, int slot, int oy0, int ox0) {
+  const bool pt = D.kind == 0;
+  if ((pt ? dark : tail_flags) == nullptr) return false;
+  const int v = pt ? D.view : D.list;
+  const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], fty = pt ? K.fl_ty[v] : K.tt_ty[v];
+  const int ty0 = oy0 / LM_FH, ty1 = min(fty - 1, (oy0 + D.tile_h - 1) / LM_FH);
+  const int tx0 = ox0 / LM_FW, tx1 = min(ftx - 1, (ox0 + D.tile_w - 1) / LM_FW);
+  const uint8_t* __restrict__ f =
+      pt ? dark + (int64_t)slot * K.fl_slot + K.fl_off[v] : tail_flags + (int64_t)slot * K.tt_slot + K.tt_off[v];
   for (int ty = ty0; ty <= ty1; ++ty)
     for (int tx = tx0; tx <= tx1; ++tx)
-      if (f[ty * K.fl_tx[v] + tx]) return false;
+      if (f[ty * ftx + tx]) return false;
   return true;
 }
 
@@ -520,6 +532,8 @@ struct RwArgs {
   int64_t tailbin_slot_bytes;
   const int32_t* tl_cnt;
   const uint32_t* tl_list;
+  const int32_t* tt_cnt;
+  const uint32_t* tt_list;
 };
 
 // One wave's work (the body of k_corr_rw and k_corr_rw_all): LM_RW_NQ
@@ -534,7 +548,7 @@ struct RwArgs {
 // dk of sub-tile qk's window row (lane + 64 k = qk NL + dk).
 template <int KW, bool UNF>
 DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const RwRun& R, float* ring) {
-  constexpr int NQ = LM_RW_NQ, NQX = LM_RW_NQX;
+  constexpr int NQ = LM_RW_NQ;
   constexpr int QX = LM_FW / PK_C;  // lanes across a sub-tile
   static_assert(LM_FH == PK_R && QX * NQ == 64, "one row of 8 lanes per 40 x 4 sub-tile");
   constexpr int STR = rw_stride(KW);
@@ -725,13 +739,15 @@ DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const 
       }
   }
   if (D.kind != 0) {
-    // tail map (the sub-tiles are one 80 x 16 tile with sub-tile 0 at its top
-    // left): 16 rows x <= 4 u32 words (the tile's origin is a multiple of 80,
-    // so 80 columns touch at most 4 words) = one word per lane, gathered in
-    // the ring, then ORed into the slot's bitmap
+    // tail map, each sub-tile on its own (listed sub-tiles are any tiles of
+    // any slots of a segment): its LM_FH rows x WPS u32 words (the origin is
+    // a multiple of LM_FW, so its columns touch at most WPS words) = one
+    // word per lane of the sub-tile, gathered in the ring, then ORed into its
+    // slot's bitmap; very few sub-tiles have a bit at all
+    constexpr int WPS = QX / LM_FH;
+    static_assert(WPS * LM_FH == QX && (LM_FW == 40 ? WPS == 2 : WPS == 4), "a sub-tile's bitmap words, one per lane");
     unsigned* s_tb = reinterpret_cast<unsigned*>(ring);
-    const int w0 = (ox0 - (q % NQX) * LM_FW) >> 5;  // the tile's first word
-    const int ty = (q / NQX) * LM_FH;               // the lane's first row in the tile
+    const int w0 = ox0 >> 5;  // the sub-tile's first word
     s_tb[lane] = 0u;
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -740,13 +756,13 @@ DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const 
       for (int c = 0; c < PK_C; ++c)
         if (bits & (1u << (r * PK_C + c))) {
           const int x = ox0 + lx * PK_C + c;
-          atomicOr(&s_tb[(ty + r) * 4 + (x >> 5) - w0], 1u << (x & 31));
+          atomicOr(&s_tb[q * QX + r * WPS + (x >> 5) - w0], 1u << (x & 31));
         }
     __builtin_amdgcn_wave_barrier();
     const unsigned v = s_tb[lane];
     unsigned* __restrict__ tb = reinterpret_cast<unsigned*>(A.tailbin + (int64_t)slot * A.tailbin_slot_bytes) +
                                 (D.list ? (int64_t)K.tail_hb * K.tail_nw : 0);
-    const int y = oy0 - (q / NQX) * LM_FH + (lane >> 2), gw = w0 + (lane & 3);  // rows from the tile's top
+    const int y = oy0 + lx / WPS, gw = w0 + lx % WPS;
     if (v && y < D.oh && gw < K.tail_nw) atomicOr(&tb[(int64_t)y * K.tail_nw + gw], v);
     return;
   }
@@ -820,15 +836,17 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(K
     const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
-    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list) {
+    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, const int32_t* __restrict__ tt_cnt,
+    const uint32_t* __restrict__ tt_list) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * rw_ring_floats(KW);
-  const RwArgs a{Kp, G, ext, ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes, tl_cnt, tl_list};
+  const RwArgs a{Kp,    G,       ext,    ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
+                 tl_cnt, tl_list, tt_cnt, tt_list};
   int d;
   RwRun R;
   if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, d, R))
+                      a.tl_list, a.tt_cnt, a.tt_list, d, R))
     return;
   rw_tile<KW, UNF>(a, d, R, ring);
 }
@@ -842,15 +860,17 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
-    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list) {
+    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, const int32_t* __restrict__ tt_cnt,
+    const uint32_t* __restrict__ tt_list) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * G.ring_floats;
-  const RwArgs a{Kp, G, ext, ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes, tl_cnt, tl_list};
+  const RwArgs a{Kp,    G,       ext,    ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
+                 tl_cnt, tl_list, tt_cnt, tt_list};
   int d;
   RwRun R;
   if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, d, R))
+                      a.tl_list, a.tt_cnt, a.tt_list, d, R))
     return;
   switch (a.K->det[d].kw_ring) {
 #define LM_KW_CASE(n)           \
@@ -878,7 +898,8 @@ __global__ __launch_bounds__(LM_CORR_THREADS) void k_corr_gen(const LmConst* __r
                                                               unsigned long long* __restrict__ keys,
                                                               int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin,
                                                               int64_t tailbin_slot_bytes,
-                                                              const uint8_t* __restrict__ dark) {
+                                                              const uint8_t* __restrict__ dark,
+                                                              const uint8_t* __restrict__ tail_flags) {
   const LmConst& K = *Kp;
   extern __shared__ float lds[];
   __shared__ int s_cnt, s_base;
@@ -886,7 +907,7 @@ __global__ __launch_bounds__(LM_CORR_THREADS) void k_corr_gen(const LmConst* __r
   const CorrTile T = corr_tile(K, G);
   const LmDet D = K.det[T.d];
   const int oy0 = T.oy0, ox0 = T.ox0;
-  if (corr_tile_dark(K, D, dark, slot, oy0, ox0)) return;
+  if (corr_tile_dark(K, D, dark, tail_flags, slot, oy0, ox0)) return;
   const int kh = D.kh, kwp = D.kwp, ch = D.chunk_rows;
   const int cols = LM_TW + kwp - 1, stride = pk_stride(cols);
   const int ew = K.ext_w[D.view];
@@ -1014,7 +1035,8 @@ __global__ __launch_bounds__(LM_F16_THREADS) __attribute__((amdgpu_waves_per_eu(
                                                             unsigned long long* __restrict__ keys,
                                                             int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin,
                                                             int64_t tailbin_slot_bytes,
-                                                            const uint8_t* __restrict__ dark) {
+                                                            const uint8_t* __restrict__ dark,
+                                                            const uint8_t* __restrict__ /* tail flags: every tail tile is computed */) {
   const LmConst& K = *Kp;
   // uint4: the dynamic area starts 16-byte aligned after the static variables
   // (with a float array it would start 8 bytes in, and every ds_read_b128 of
@@ -1025,7 +1047,7 @@ __global__ __launch_bounds__(LM_F16_THREADS) __attribute__((amdgpu_waves_per_eu(
   const CorrTile T = corr_tile(K, G);
   const LmDet D = K.det[T.d];
   const int oy0 = T.oy0, ox0 = T.ox0, kh = D.kh;
-  if (corr_tile_dark(K, D, dark, slot, oy0, ox0)) return;
+  if (corr_tile_dark(K, D, dark, nullptr, slot, oy0, ox0)) return;
   constexpr int cols = f16_cols(NCH), STR = f16_stride(cols);
   const int rows = LM_F16_TH + kh - 1;
   _Float16* __restrict__ img = reinterpret_cast<_Float16*>(lds_f16);
@@ -1257,12 +1279,12 @@ hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t
     void* args[] = {(void*)&K,       (void*)&G,    (void*)&ext,     (void*)&ext_slot_bytes,
                     (void*)&weights, (void*)&s0,   (void*)&nslots,  (void*)&keys,
                     (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes, (void*)&dk.cnt,
-                    (void*)&dk.list};
+                    (void*)&dk.list, (void*)&dk.tail_cnt, (void*)&dk.tail_list};
     return hipLaunchKernel(fn, dim3((waves + LM_RW_WAVES - 1) / LM_RW_WAVES), dim3(LM_RW_THREADS), args, lds, st);
   }
   void* args[] = {(void*)&K,     (void*)&G,       (void*)&ext,     (void*)&ext_slot_bytes,           (void*)&weights,
                   (void*)&s0,    (void*)&keys,    (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes,
-                  (void*)&dk.flags};
+                  (void*)&dk.flags, (void*)&dk.tail_flags};
   return hipLaunchKernel(fn, grid, dim3(threads), args, lds, st);
 }
 

@@ -7,6 +7,8 @@
 //   k_ingest      calibration gather + flip + LUT (+ the in-place grey-level LUT of
 //                 transform_gray_values) -> extended padded crops (u8)
 //                 :1316-1327 (correctImage :1337-1406), cropBoundingBox :1408-1478
+//   k_tail_bound  the tail detectors' 40 x 4 tiles whose scores are not proven
+//                 negative (lm_tail_bound.h), listed and flagged for k_corr
 //   k_corr        all six filter2D detectors, fp32 row-major FMA chains, LDS-tiled;
 //                 epilogue: brightness mask + score>0 compaction / tail binarisation
 //                 :845, :860, :2575-2576, :782, :817, :849, :864, :2593-2598
@@ -30,6 +32,7 @@
 #include "lm_introsort.h"
 
 #include "lm_dev_common.h"
+#include "lm_tail_bound.h"
 
 // ------------------------------------------------------------------ helpers
 
@@ -631,6 +634,108 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
     pb[15] = wall_clock64();
   }
 #undef ING_PROF
+}
+
+// ------------------------------------------------------------ k_tail_bound
+// The tail detectors' tiles that have to be computed.  The pipeline uses only
+// the sign of a tail score, and k_ingest has zeroed the tail bitmaps, so a
+// LM_FW x LM_FH tile whose scores are all provably < 0 (lm_tail_bound.h: an
+// upper bound from per-row pixel ranges, with the fp32 chain's rounding error
+// added) is left out.  One workgroup per (slot, tail detector): the
+// detector's window of the ext crop ((oh + kh - 1) x (ow + kw - 1) bytes)
+// reduced to pixel ranges per row and block of 8 columns, those to ranges per
+// row and tile column, then the bound per tile; the tiles not proven are
+// flagged (one byte each, for k_corr_gen) and appended to the detector's list
+// segments (for the ring kernels), in the point detectors' entry format and
+// segment scheme (k_ingest).  A detector without a usable bound (tb_skip = 0:
+// rho <= 0, non-finite weights, a window beyond the LDS) lists every tile.
+static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the tail bound's tiles are the dark-tile grid's");
+#define LM_TB_THREADS 256
+__global__ __launch_bounds__(LM_TB_THREADS) void k_tail_bound(const LmConst* __restrict__ Kp,
+                                                              const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
+                                                              int s0, const double* __restrict__ tbc,
+                                                              uint8_t* __restrict__ flags, int32_t* __restrict__ tt_cnt,
+                                                              uint32_t* __restrict__ tt_list) {
+  const LmConst& K = *Kp;
+  extern __shared__ uint8_t tb_lds[];
+  __shared__ int s_n, s_k, s_base;
+  const int t = (int)blockIdx.y, slot = s0 + (int)blockIdx.x;
+  const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+  const LmDet& D = K.det[t ? DET_TAIL_S : DET_TAIL_B];
+  const int ftx = K.tt_tx[t], ntile = ftx * K.tt_ty[t];
+  uint8_t* __restrict__ fl = flags + (int64_t)slot * K.tt_slot + K.tt_off[t];
+  if (tid == 0) {
+    s_n = 0;
+    s_k = 0;
+  }
+  if (K.tb_skip[t]) {
+    const int kh = D.kh, kw = D.kw, ew = K.ext_w[D.view];
+    const int rows = D.oh + kh - 1, wcols = D.ow + kw - 1, nblk = (wcols + LM_TB_BLK - 1) / LM_TB_BLK;
+    uint8_t* bmax = tb_lds;
+    uint8_t* bmin = bmax + rows * nblk;
+    uint8_t* rmax = bmin + rows * nblk;
+    uint8_t* rmin = rmax + rows * ftx;
+    const uint8_t* __restrict__ win = ext + (int64_t)slot * ext_slot_bytes +
+                                      (D.view ? (int64_t)K.ext_h[0] * K.ext_w[0] : 0) + (int64_t)D.in_y * ew + D.in_x;
+    static_assert(LM_TB_BLK == 8, "one 8-byte load per block");
+    // ranges per (row, block); a row's last block ends at the window's last
+    // column (the load may run a few bytes past it, inside the ext buffer)
+    // (batching eight of a thread's loads before their use changed nothing:
+    // 175 vs 178 us per launch among eight contexts' kernels, profiles/tailskip/)
+    for (int e = tid; e < rows * nblk; e += T) {
+      const int r = e / nblk, b = e - r * nblk;
+      uint2 v;
+      __builtin_memcpy(&v, win + (int64_t)r * ew + LM_TB_BLK * b, 8);
+      const int nv = min(LM_TB_BLK, wcols - LM_TB_BLK * b);
+      unsigned mx = 0u, mn = 255u;
+#pragma unroll
+      for (int k = 0; k < LM_TB_BLK; ++k) {
+        const unsigned p = ((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 0xFFu;
+        if (k < nv) {
+          mx = max(mx, p);
+          mn = min(mn, p);
+        }
+      }
+      bmax[e] = (uint8_t)mx;
+      bmin[e] = (uint8_t)mn;
+    }
+    __syncthreads();
+    // ranges per (row, tile column): the blocks of lm_tb_span's columns
+    for (int e = tid; e < rows * ftx; e += T) {
+      const int r = e / ftx, tx = e - r * ftx;
+      int c0, c1;
+      lm_tb_span(tx, kw, D.ow, &c0, &c1);
+      unsigned mx = 0u, mn = 255u;
+      for (int b = c0 / LM_TB_BLK; b < (c1 + LM_TB_BLK - 1) / LM_TB_BLK; ++b) {
+        mx = max(mx, (unsigned)bmax[r * nblk + b]);
+        mn = min(mn, (unsigned)bmin[r * nblk + b]);
+      }
+      rmax[e] = (uint8_t)mx;
+      rmin[e] = (uint8_t)mn;
+    }
+    __syncthreads();
+    const double* __restrict__ P = tbc + K.tb_off[t];
+    int mine = 0;
+    for (int i = tid; i < ntile; i += T) {
+      const bool skip = lm_tb_tile_skip(rmax, rmin, ftx, D.oh, kh, i / ftx, i % ftx, P, P + kh, K.tb_bias[t]);
+      fl[i] = skip ? 0 : 1;
+      mine += skip ? 0 : 1;
+    }
+    if (mine) atomicAdd(&s_n, mine);
+  } else {
+    for (int i = tid; i < ntile; i += T) fl[i] = 1;
+    if (tid == 0) s_n = ntile;
+  }
+  __syncthreads();
+  // this workgroup's list segment and its counter, as in k_ingest
+  const int G = ((int)gridDim.x + LM_INGEST_FB - 1) / LM_INGEST_FB;
+  const int c = ((int)blockIdx.x / LM_INGEST_FB) * LM_TL_NC / G;
+  if (tid == 0) s_base = s_n ? atomicAdd(&tt_cnt[t * LM_TL_NC + c], s_n) : 0;
+  __syncthreads();
+  uint32_t* __restrict__ out =
+      tt_list + (int64_t)t * K.tt_stride + (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base;
+  for (int i = tid; i < ntile; i += T)  // (each thread re-reads the flags it wrote)
+    if (fl[i]) out[atomicAdd(&s_k, 1)] = ((uint32_t)slot << 16) | (uint32_t)i;
 }
 
 #include "lm_corr.h"  // the correlation kernels are their own translation unit (lm_corr.hip)
@@ -2462,12 +2567,14 @@ __global__ __launch_bounds__(256) void k_prep(const LmSlot* __restrict__ h_slots
                                               int32_t* __restrict__ npos, int32_t* __restrict__ err,
                                               const LmConst* __restrict__ Kp, unsigned long long* __restrict__ keys,
                                               const LmSlotOut* __restrict__ prev_hdr, int prev_slot,
-                                              LmSlotOut* __restrict__ hdr, int32_t* __restrict__ dark_cnt) {
+                                              LmSlotOut* __restrict__ hdr, int32_t* __restrict__ dark_cnt,
+                                              int32_t* __restrict__ tail_cnt) {
   if (blockIdx.x == 1) {
     carry_block(*Kp, keys, prev_hdr, prev_slot, hdr);
     return;
   }
   if (dark_cnt) dark_cnt[threadIdx.x] = 0;  // k_ingest's bright-tile counters (4 LM_TL_NC = blockDim.x)
+  if (tail_cnt && threadIdx.x < 2 * LM_TL_NC) tail_cnt[threadIdx.x] = 0;  // k_tail_bound's tail-tile counters
   for (int i = threadIdx.x; i < ns; i += blockDim.x) {
     slots[i] = h_slots[i];
     fptr[i] = h_fptr[i];

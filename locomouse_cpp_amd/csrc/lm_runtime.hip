@@ -107,6 +107,9 @@ struct Lane {
   DevBuf<uint8_t> dark_flags;  // dark tiles (CorrDark): flag bytes, bright-tile lists and counts
   DevBuf<uint32_t> dark_list;
   DevBuf<int32_t> dark_cnt;
+  DevBuf<uint8_t> tail_flags;  // tail tiles not proven non-positive (k_tail_bound): flag bytes, lists and counts
+  DevBuf<uint32_t> tail_list;
+  DevBuf<int32_t> tail_cnt;
   HostBuf<int32_t> h_cnt;   // debug bit 1: dark_cnt of the submitted batch, copied on its stream
   bool h_cnt_valid = false;
   DevBuf<long long> kprof;  // LM_KPROF=1: kernel phase timestamps
@@ -209,6 +212,10 @@ struct lm_ctx {
   int64_t tail_ws_slot = 0;     // its workspace bytes per slot
   bool kprof_on = false;
   bool dark_on = true;  // skip the point detectors' dark tiles (LM_CORR_DARK=0: compute every tile)
+  // skip the tail detectors' tiles that lm_tail_bound.h proves non-positive
+  // (LM_CORR_TAILSKIP=0: compute every tail tile; never in the f16 mode)
+  bool tailskip_on = true;
+  DevBuf<double> tb_const;  // the bound's P_i, N_i per tail detector (LmConst::tb_off)
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
   DevBuf<uint8_t> handoff;     // two frames: the last frame of submitted batch k in slot k & 1
@@ -685,6 +692,35 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
     for (int i = 0; i < D.kh; ++i)
       for (int j = 0; j < D.kw; ++j) wts[(size_t)D.w_off + i * D.kwp + j] = (float)dets[d]->weights[(size_t)i * D.kw + j];
   }
+  // tail tiles: the grid of LM_FW x LM_FH tiles per tail detector and the
+  // bound's constants (lm_tail_bound.h) from the fp32 weights the kernels use
+  std::vector<double> tbc;
+  if (const char* v = getenv("LM_CORR_TAILSKIP")) c->tailskip_on = atoi(v) != 0;
+  if (su->corr_precision == LM_CORR_F16) c->tailskip_on = false;
+  {
+    int o = 0, mt = 0;
+    for (int t = 0; t < 2; ++t) {
+      const LmDet& D = K.det[t ? DET_TAIL_S : DET_TAIL_B];
+      K.tt_tx[t] = (D.ow + LM_FW - 1) / LM_FW;
+      K.tt_ty[t] = (D.oh + LM_FH - 1) / LM_FH;
+      K.tt_off[t] = o;
+      o += (K.tt_tx[t] * K.tt_ty[t] + 3) / 4 * 4;
+      mt = std::max(mt, K.tt_tx[t] * K.tt_ty[t]);
+      K.tb_off[t] = (int32_t)tbc.size();
+      tbc.resize(tbc.size() + 2 * (size_t)D.kh);
+      K.tb_skip[t] = lm_tb_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.delta, tbc.data() + K.tb_off[t],
+                                   tbc.data() + K.tb_off[t] + D.kh, &K.tb_bias[t]);
+      // k_tail_bound's pixel ranges of the detector's window, in LDS
+      const int64_t rows = (int64_t)D.oh + D.kh - 1, nblk = (D.ow + D.kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK;
+      const int64_t lds = 2 * rows * (nblk + K.tt_tx[t]);
+      if (lds > 64 * 1024) K.tb_skip[t] = 0;
+      K.tb_lds[t] = K.tb_skip[t] ? (int32_t)lds : 0;
+    }
+    K.tt_slot = o;
+    K.tt_stride = c->nslots * mt;
+    // (list entries hold slot << 16 | tile)
+    if (mt > 65535 || c->nslots > 65535) c->tailskip_on = false;
+  }
   // LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
   // scaled by 2^s so that the largest |w| lands in [2^14, 2^15) (the rounding
   // is then relative and no weight of interest is subnormal; 2^s and 2^-s
@@ -737,6 +773,8 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   COPY_SYNC(c->cal.p, su->ind_warp_mapping, nc * sizeof(int32_t), hipMemcpyHostToDevice, cs);
   c->weights.alloc(wts.size());
   COPY_SYNC(c->weights.p, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice, cs);
+  c->tb_const.alloc(tbc.size());
+  COPY_SYNC(c->tb_const.p, tbc.data(), tbc.size() * sizeof(double), hipMemcpyHostToDevice, cs);
   if (!w16.empty()) {
     c->weights16.alloc(w16.size());
     COPY_SYNC(c->weights16.p, w16.data(), w16.size() * sizeof(_Float16), hipMemcpyHostToDevice, cs);
@@ -788,6 +826,13 @@ void lane_alloc(lm_ctx* c, Lane& L) {
     L.dark_list.alloc((size_t)2 * K.tl_stride);
     L.dark_cnt.alloc(4 * LM_TL_NC);
     L.h_cnt.alloc(4 * LM_TL_NC);
+  }
+  if (c->tailskip_on) {
+    L.tail_flags.alloc((size_t)K.tt_slot * ns);
+    SET_SYNC(L.tail_flags.p, 0, (size_t)K.tt_slot * ns, st);
+    L.tail_list.alloc((size_t)2 * K.tt_stride);
+    L.tail_cnt.alloc(2 * LM_TL_NC);
+    SET_SYNC(L.tail_cnt.p, 0, 2 * LM_TL_NC * sizeof(int32_t), st);
   }
   L.err.alloc(16);
   L.frame_ptr.alloc(ns);
@@ -1088,6 +1133,11 @@ CorrDark lane_dark(const lm_ctx* c, Lane& L) {
     d.cnt = L.dark_cnt.p;
     d.list = L.dark_list.p;
   }
+  if (c->tailskip_on) {
+    d.tail_flags = L.tail_flags.p;
+    d.tail_cnt = L.tail_cnt.p;
+    d.tail_list = L.tail_list.p;
+  }
   return d;
 }
 
@@ -1106,7 +1156,7 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
     // block 1: k_carry (a rerun keeps slot 0's staged candidates)
     k_prep<<<do_carry ? 2 : 1, 256, 0, st>>>(L.h_slots.d, L.h_frame_ptr.d, L.h_ctl.d, n + 1, L.slots.p, L.frame_ptr.p,
                                              A.ctl.p, L.npos.p, L.err.p, dK, L.keys.p, L.arena[P.prv].hdr.p, P.last_n,
-                                             A.hdr.p, L.dark_cnt.p);
+                                             A.hdr.p, L.dark_cnt.p, L.tail_cnt.p);
     T.begin("k_minmax");
     k_minmax<<<dim3(LM_MM_SPLIT, n + 1 - s_lut0), LM_MM_THREADS, 0, st>>>(L.frame_ptr.p, c->bkg.p, c->npix, s_lut0,
                                                                         L.mm.p);
@@ -1127,6 +1177,12 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
                                         c->ext_slot_bytes, reinterpret_cast<unsigned*>(L.tailbin.p), L.smap.p, L.sbkg.p,
                                         L.skey.p, dk.flags, dk.cnt, dk.list, kpi);
     T.end();
+    if (dk.tail_cnt) {  // the tail detectors' tiles that the correlation has to compute
+      T.begin("k_tail_bound");
+      k_tail_bound<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, (size_t)std::max(K.tb_lds[0], K.tb_lds[1]), st>>>(
+          dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.tail_flags, dk.tail_cnt, dk.tail_list);
+      T.end();
+    }
   }
   if (part == 1 || part < 0) {
     T.begin("k_corr");
@@ -1871,6 +1927,39 @@ LM_API lm_status lm_debug_scores(lm_ctx* ctx, int32_t f, int32_t det, float* out
   return guarded([&] {
     HIPCHK(hipSetDevice(ctx->device));
     COPY_SYNC(out, L.dbg.p + (int64_t)(f + 1) * ctx->dbg_slot_floats + ctx->dbg_off[det], sizeof(float) * rows * cols,
+              hipMemcpyDeviceToHost, L.stream);
+  });
+}
+
+LM_API lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  for (int k = 0; k < 4; ++k) out[k] = -1;
+  if (!ctx->tailskip_on) return LM_OK;
+  const Lane* Lp = delivered_lane(ctx);
+  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
+  const Lane& L = *Lp;
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t h[2 * LM_TL_NC];
+    COPY_SYNC(h, L.tail_cnt.p, sizeof(h), hipMemcpyDeviceToHost, L.stream);
+    for (int t = 0; t < 2; ++t) {
+      out[2 * t] = std::accumulate(h + t * LM_TL_NC, h + (t + 1) * LM_TL_NC, 0);
+      out[2 * t + 1] = ctx->delivered.slots * ctx->K.tt_tx[t] * ctx->K.tt_ty[t];
+    }
+  });
+}
+
+LM_API lm_status lm_debug_tail_tiles(lm_ctx* ctx, int32_t f, int32_t view, uint8_t* out, int32_t rows, int32_t cols) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (!ctx->tailskip_on) return fail(LM_ERR_INVALID_ARGUMENT, "tail-tile skipping is off");
+  const Lane* Lp = delivered_lane(ctx);
+  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
+  const Lane& L = *Lp;
+  if (f < 0 || f >= L.batch_n || view < 0 || view > 1) return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
+  if (rows != ctx->K.tt_ty[view] || cols != ctx->K.tt_tx[view]) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    COPY_SYNC(out, L.tail_flags.p + (int64_t)(f + 1) * ctx->K.tt_slot + ctx->K.tt_off[view], (size_t)rows * cols,
               hipMemcpyDeviceToHost, L.stream);
   });
 }

@@ -1,0 +1,122 @@
+/*
+ * lm_tail_bound.h — an upper bound on a tail detector's scores over one
+ * 40 x 4 output tile, from per-row pixel ranges (plain C++: the host runtime,
+ * the k_tail_bound kernel and tests/cpp/tail_bound_check.cpp share it).
+ *
+ * The pipeline uses only the sign of a tail score (threshold(> 0), then
+ * connected components), and k_ingest zeroes the tail bitmaps, so a tile
+ * whose scores are all provably < 0 need not be computed.
+ *
+ * The detector: fp32 weights w[i][j] (kh x kw), start value delta, score
+ *     s(y, x) = delta + sum_ij w[i][j] I(y + i, x + j)
+ * over the window I (u8; output (0, 0) reads I(0 .. kh-1, 0 .. kw-1)).
+ *
+ * The bound.  Tile (ty, tx) holds the outputs y in [4 ty, y1), x in
+ * [40 tx, x1), clipped to oh x ow.  At tap (i, j) every one of them reads a
+ * pixel in window rows 4 ty + i .. y1 - 1 + i and columns 40 tx .. x1 - 2 + kw.
+ * With M_i / m_i the largest / smallest pixel in that rectangle (here over
+ * the column span rounded up to a multiple of LM_TB_BLK, which only widens
+ * it), P_i = sum_j max(w[i][j], 0) and N_i = sum_j max(-w[i][j], 0):
+ *     s(y, x) <= U = delta + sum_i (P_i M_i - N_i m_i)        (exact arithmetic)
+ * since w p <= max(w, 0) M - max(-w, 0) m for every m <= p <= M.
+ *
+ * Rounding.  The kernels (and the reference) evaluate the score as an fp32
+ * chain acc = fl(acc + w p) over n = kh kw taps, fused or as a rounded
+ * product and a rounded sum.  By the standard running-error bound the
+ * computed value differs from the exact one by at most
+ *     gamma_(n+1) (|delta| + sum |w| 255),  gamma_k = k u / (1 - k u), u = 2^-24,
+ * plus n underflow errors of at most 2^-126 each; gamma = 2 n 2^-23 = 4 n u
+ * covers gamma_(n+1) for n < 2^20.  lm_tb_prepare() adds that, and 1e-6
+ * relative for the double evaluation of U and the rounding of P_i / N_i
+ * (each off by less than 1e-12 relative), to delta: `bias`.  The tile is
+ * skipped iff  bias + sum_i (P_i M_i - N_i m_i) < 0  in double; every
+ * computed score of the tile is then < 0.
+ * Never skipped: non-finite weights, delta >= 0 or not finite, n >= 2^20,
+ * sums beyond 1e30.
+ */
+#ifndef LM_TAIL_BOUND_H
+#define LM_TAIL_BOUND_H
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LM_TB_HD __host__ __device__
+#else
+#define LM_TB_HD
+#endif
+
+#define LM_TB_W 40   // tile columns (the dark-tile grid: LM_FW)
+#define LM_TB_H 4    // tile rows (LM_FH)
+#define LM_TB_BLK 8  // pixel ranges are first taken over aligned blocks of 8 window columns
+
+// P[kh], N[kh] and bias of a detector (row i's weights at w + i * wstride).
+// Returns 1 when its tiles may be skipped, 0 when every tile must be computed.
+LM_TB_HD inline int lm_tb_prepare(const float* w, int kh, int kw, int wstride, float delta, double* P, double* N,
+                                  double* bias) {
+  int ok = 1;
+  double sabs = 0.0;
+  for (int i = 0; i < kh; ++i) {
+    double p = 0.0, n = 0.0;
+    for (int j = 0; j < kw; ++j) {
+      const double v = (double)w[i * wstride + j];
+      if (!(v - v == 0.0)) ok = 0;  // NaN or infinite
+      if (v > 0.0) p += v;
+      else n -= v;
+    }
+    P[i] = p * (1.0 + 1e-12);  // rounded up
+    N[i] = n * (1.0 - 1e-12);  // rounded down (it is subtracted)
+    sabs += p + n;
+  }
+  const double d = (double)delta;
+  const double taps = (double)kh * (double)kw;
+  const double S = (d < 0.0 ? -d : d) + 255.0 * sabs;
+  const double gamma = 2.0 * taps * (1.0 / 8388608.0);  // 2 n 2^-23
+  const double margin = gamma * S + 1e-6 * S + taps * 1.2e-38;
+  *bias = d + margin;
+  if (!(d < 0.0) || !(d - d == 0.0) || !(taps < 1048576.0) || !(S < 1e30)) ok = 0;
+  return ok;
+}
+
+// Window columns [c0, c1) whose pixels tile column tx's outputs read: from
+// 40 tx to the last tap of the last output inside ow, rounded up to a block
+// boundary and clipped to the window's ow + kw - 1 columns.
+LM_TB_HD inline void lm_tb_span(int tx, int kw, int ow, int* c0, int* c1) {
+  const int x1 = (tx + 1) * LM_TB_W < ow ? (tx + 1) * LM_TB_W : ow;
+  const int end = (x1 - 1 + kw + LM_TB_BLK - 1) / LM_TB_BLK * LM_TB_BLK;
+  *c0 = tx * LM_TB_W;
+  *c1 = end < ow + kw - 1 ? end : ow + kw - 1;
+}
+
+// Largest and smallest pixel of row[c0 .. c1 - 1].
+LM_TB_HD inline void lm_tb_row_range(const uint8_t* row, int c0, int c1, uint8_t* mx, uint8_t* mn) {
+  unsigned a = 0u, b = 255u;
+  for (int c = c0; c < c1; ++c) {
+    const unsigned v = row[c];
+    a = v > a ? v : a;
+    b = v < b ? v : b;
+  }
+  *mx = (uint8_t)a;
+  *mn = (uint8_t)b;
+}
+
+// The predicate for tile (ty, tx) from the row ranges rmax / rmin
+// ([window row][tile column], ftx tile columns per row): true = every score
+// of the tile is < 0.
+LM_TB_HD inline bool lm_tb_tile_skip(const uint8_t* rmax, const uint8_t* rmin, int ftx, int oh, int kh, int ty, int tx,
+                                     const double* P, const double* N, double bias) {
+  const int y0 = ty * LM_TB_H;
+  const int nr = (y0 + LM_TB_H < oh ? y0 + LM_TB_H : oh) - y0;  // output rows of the tile inside oh
+  double U = bias;
+  for (int i = 0; i < kh; ++i) {
+    unsigned a = 0u, b = 255u;
+    for (int r = 0; r < nr; ++r) {
+      const unsigned x = rmax[(y0 + i + r) * ftx + tx], n = rmin[(y0 + i + r) * ftx + tx];
+      a = x > a ? x : a;
+      b = n < b ? n : b;
+    }
+    U += P[i] * (double)a - N[i] * (double)b;
+  }
+  return U < 0.0;
+}
+
+#endif  // LM_TAIL_BOUND_H

@@ -26,7 +26,7 @@ EXPORTED = (
     "lm_bb_stream", "lm_host_alloc", "lm_host_free",
     "lm_detect_submit", "lm_detect_submit_device", "lm_detect_collect", "lm_ctx_lanes", "lm_ctx_pending",
     "lm_debug_corr_work", "lm_debug_batch_slots", "lm_debug_dark_tile_width",
-    "lm_debug_dark_tile_height",
+    "lm_debug_dark_tile_height", "lm_debug_tail_work", "lm_debug_tail_tiles",
 )
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -175,6 +175,8 @@ def lib():
                                             C.POINTER(C.c_double), C.c_int32]
         L.lm_debug_kernel_spans.restype = C.c_int32
         L.lm_debug_corr_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.lm_debug_tail_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.lm_debug_tail_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
         L.lm_debug_batch_slots.argtypes = [C.c_void_p]
         L.lm_debug_batch_slots.restype = C.c_int32
         L.lm_synth_frames_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
@@ -372,6 +374,24 @@ class Context:
         out = (C.c_int32 * 4)()
         _check(lib().lm_debug_corr_work(self._h, out))
         return None if out[0] < 0 else {"tiles": (out[0], out[1]), "outputs": (out[2], out[3])}
+
+    def tail_work(self):
+        """Tail tiles listed for computing and all tail tiles of the last
+        batch, per tail detector (lm_debug_tail_work), or None with the skip
+        off."""
+        out = (C.c_int32 * 4)()
+        _check(lib().lm_debug_tail_work(self._h, out))
+        return None if out[0] < 0 else {"listed": (out[0], out[2]), "total": (out[1], out[3])}
+
+    def tail_tiles(self, f, view):
+        """[tile rows, tile columns] u8: 1 where frame f's tile of tail
+        detector `view` (0 bottom, 1 side) was listed (lm_debug_tail_tiles)."""
+        g = self.geometry()
+        tw, th = self.dark_tile_shape()
+        oh = (g.bb_side_mouse if view else g.bb_bottom_mouse).height
+        out = np.zeros((-(-oh // th), -(-g.tail_box_width // tw)), dtype=np.uint8)
+        _check(lib().lm_debug_tail_tiles(self._h, f, view, out.ctypes.data, out.shape[0], out.shape[1]))
+        return out
 
     def batch_slots(self):
         """Frame slots the last collected batch processed (n, or n + 1 with
