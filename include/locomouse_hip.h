@@ -363,6 +363,24 @@ lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out);
  * ceil(ow / tile width) of its outputs. */
 lm_status lm_debug_tail_tiles(lm_ctx* ctx, int32_t f, int32_t view, uint8_t* out, int32_t rows, int32_t cols);
 
+/* Point-detector work of the last collected batch.  A point score is kept
+ * only when it is > 0 under a mouse pixel > 25 (LocoMouse_class.cpp:782-864),
+ * so a bright tile of the dark-tile grid whose scores the same bound proves
+ * < 0 is not computed either (LM_CORR_POINTSKIP=0 in the environment at
+ * lm_ctx_create: compute every bright tile).  For paw_bottom, snout_bottom,
+ * paw_side and snout_side in turn, out[2 k] = tiles listed for computing and
+ * out[2 k + 1] = bright tiles over the batch's slots; -1 with the skip off
+ * (also in the LM_CORR_F16 mode and with LM_CORR_DARK=0).  Reads the lane the
+ * batch ran on, like lm_debug_tail_work. */
+lm_status lm_debug_point_work(lm_ctx* ctx, int32_t* out);
+
+/* The flag bytes behind those counts for frame f of the last collected batch:
+ * out[ty * cols + tx] = 1 when tile (ty, tx) of point detector `det` (its
+ * lm_debug_scores id: 0 paw_bottom, 1 snout_bottom, 3 paw_side, 4 snout_side)
+ * was listed; rows x cols = ceil(oh / tile height) x ceil(ow / tile width) of
+ * its outputs. */
+lm_status lm_debug_point_tiles(lm_ctx* ctx, int32_t f, int32_t det, uint8_t* out, int32_t rows, int32_t cols);
+
 /* The dark-tile grid: tiles of lm_debug_dark_tile_width() x
  * lm_debug_dark_tile_height() outputs (40 x 4 in the default build; 40 x 8
  * and 80 x 8 as build options, -DLM_FH=8 / -DLM_FW=80). */

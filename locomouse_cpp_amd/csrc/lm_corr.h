@@ -127,8 +127,12 @@ const void* corr_kernel_f16(int kw);           // nullptr when kw is too wide
 // per (slot, view, tile), the bright tiles' list per view and their counts.
 // All null: every tile is computed (LM_CORR_DARK=0).
 // tail_*: the same for the tail detectors' tiles that are not proven
-// non-positive (written by k_tail_bound); all null: every tail tile is
+// non-positive (written by k_tile_bound); all null: every tail tile is
 // computed (LM_CORR_TAILSKIP=0, the f16 mode).
+// pt_*: the same per point detector (list id) for its bright tiles that are
+// not proven non-positive (k_tile_bound); when set, the fp32 kernels take a
+// point detector's tiles from these instead of the view's; all null: every
+// bright tile is computed (LM_CORR_POINTSKIP=0, LM_CORR_DARK=0, the f16 mode).
 struct CorrDark {
   uint8_t* flags = nullptr;
   int32_t* cnt = nullptr;
@@ -136,6 +140,9 @@ struct CorrDark {
   uint8_t* tail_flags = nullptr;
   int32_t* tail_cnt = nullptr;
   uint32_t* tail_list = nullptr;
+  uint8_t* pt_flags = nullptr;
+  int32_t* pt_cnt = nullptr;
+  uint32_t* pt_list = nullptr;
 };
 // Launch the correlation for one detector group (`weights`: the fp32 rows, or
 // the f16 B fragments for k_corr_f16).  Ring kernels take one wave per tile

@@ -246,9 +246,13 @@ struct RwRun {
 // time from the list segments k_ingest filled (segment c: tl_cnt[view
 // LM_TL_NC + c] tiles, ceil(/ LM_RW_NQ) waves), packed densely: a wave finds
 // its segment with one scan over the 64 counters, one per lane.  With
-// tail-tile lists (tt_cnt != nullptr) a tail detector's waves take the tiles
-// k_tail_bound could not prove non-positive from its segments in the same
-// way.  The group's wave count is known on the device only, so the grid is
+// per-detector point lists (tl_per_det: tl_cnt / tl_list are k_tile_bound's,
+// indexed by list id) the waves take the detector's own tiles instead: its
+// view's bright tiles that are not proven non-positive, a subset of them, in
+// the same segments.  With tail-tile lists (tt_cnt != nullptr) a tail
+// detector's waves take the tiles k_tile_bound could not prove non-positive
+// from its segments in the same way.
+// The group's wave count is known on the device only, so the grid is
 // sized for every 80 x 16 tile and the waves past the last group's count
 // (whole workgroups at the grid's end) return.  That is enough: a segment
 // holds the tiles of whole slots, a slot lists at most the 8 sub-tile places
@@ -267,7 +271,8 @@ struct RwRun {
 // between the working ones; the dense layout has neither.
 static_assert(LM_TL_NC == 64, "one list counter per lane");
 DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
-                        const uint32_t* tl_list, const int32_t* tt_cnt, const uint32_t* tt_list, int& d, RwRun& R) {
+                        const uint32_t* tl_list, int tl_per_det, const int32_t* tt_cnt, const uint32_t* tt_list, int& d,
+                        RwRun& R) {
   constexpr int NQ = LM_RW_NQ;
   const int lane = threadIdx.x & 63;
   int base = 0;
@@ -279,10 +284,11 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
     const int nt = G.tile_end[k] - (k ? G.tile_end[k - 1] : 0);
     const bool pt = tl_cnt != nullptr && D.kind == 0;  // bright tiles of the view
     if (pt || (tt_cnt != nullptr && D.kind != 0)) {    // or the tail detector's tiles that are not proven
-      const int v = pt ? D.view : D.list;
+      const int v = pt ? D.view : D.list;  // the tile grid (a view's, or a tail detector's)
+      const int li = pt && !tl_per_det ? v : D.list;  // the list: the view's, or the detector's own
       const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], ntile = ftx * (pt ? K.fl_ty[v] : K.tt_ty[v]);
-      const uint32_t* lst = pt ? tl_list + (int64_t)v * K.tl_stride : tt_list + (int64_t)v * K.tt_stride;
-      const int cn = (pt ? tl_cnt : tt_cnt)[v * LM_TL_NC + lane];  // segment `lane`'s tiles
+      const uint32_t* lst = pt ? tl_list + (int64_t)li * K.tl_stride : tt_list + (int64_t)li * K.tt_stride;
+      const int cn = (pt ? tl_cnt : tt_cnt)[li * LM_TL_NC + lane];  // segment `lane`'s tiles
       const int wv = (cn + NQ - 1) / NQ;
       int P = wv;  // inclusive scan: waves of segments 0 .. lane
 #pragma unroll
@@ -320,8 +326,10 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
 
 // A workgroup tile of a point detector (k_corr_gen, k_corr_f16) whose flag
 // tiles are all dark has no output that survives the mask.
-// The same for a tail detector (k_corr_gen) and the tiles k_tail_bound has
-// proven non-positive (flag 0): none of its outputs sets a bit.
+// The same for a tail detector (k_corr_gen) and the tiles k_tile_bound has
+// proven non-positive (flag 0): none of its outputs sets a bit.  `dark` may
+// also be the detector's own plane of k_tile_bound's point flags (the same
+// layout: its bright tiles that are not proven non-positive, LmConst::pt_plane).
 DEV bool corr_tile_dark(const LmConst& K, const LmDet& D, const uint8_t* __restrict__ dark,
                         const uint8_t* __restrict__ tail_flags, int slot, int oy0, int ox0) {
   const bool pt = D.kind == 0;
@@ -532,6 +540,7 @@ struct RwArgs {
   int64_t tailbin_slot_bytes;
   const int32_t* tl_cnt;
   const uint32_t* tl_list;
+  int32_t tl_per_det;
   const int32_t* tt_cnt;
   const uint32_t* tt_list;
 };
@@ -836,17 +845,17 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(K
     const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
-    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, const int32_t* __restrict__ tt_cnt,
-    const uint32_t* __restrict__ tt_list) {
+    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, int tl_per_det,
+    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * rw_ring_floats(KW);
   const RwArgs a{Kp,    G,       ext,    ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
-                 tl_cnt, tl_list, tt_cnt, tt_list};
+                 tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list};
   int d;
   RwRun R;
   if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, a.tt_cnt, a.tt_list, d, R))
+                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, d, R))
     return;
   rw_tile<KW, UNF>(a, d, R, ring);
 }
@@ -860,17 +869,17 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
-    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, const int32_t* __restrict__ tt_cnt,
-    const uint32_t* __restrict__ tt_list) {
+    const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, int tl_per_det,
+    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * G.ring_floats;
   const RwArgs a{Kp,    G,       ext,    ext_slot_bytes, weights, s0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
-                 tl_cnt, tl_list, tt_cnt, tt_list};
+                 tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list};
   int d;
   RwRun R;
   if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, a.tt_cnt, a.tt_list, d, R))
+                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, d, R))
     return;
   switch (a.K->det[d].kw_ring) {
 #define LM_KW_CASE(n)           \
@@ -899,7 +908,8 @@ __global__ __launch_bounds__(LM_CORR_THREADS) void k_corr_gen(const LmConst* __r
                                                               int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin,
                                                               int64_t tailbin_slot_bytes,
                                                               const uint8_t* __restrict__ dark,
-                                                              const uint8_t* __restrict__ tail_flags) {
+                                                              const uint8_t* __restrict__ tail_flags,
+                                                              const uint8_t* __restrict__ pt_flags) {
   const LmConst& K = *Kp;
   extern __shared__ float lds[];
   __shared__ int s_cnt, s_base;
@@ -907,7 +917,9 @@ __global__ __launch_bounds__(LM_CORR_THREADS) void k_corr_gen(const LmConst* __r
   const CorrTile T = corr_tile(K, G);
   const LmDet D = K.det[T.d];
   const int oy0 = T.oy0, ox0 = T.ox0;
-  if (corr_tile_dark(K, D, dark, tail_flags, slot, oy0, ox0)) return;
+  // a point detector's flags: its own plane of k_tile_bound's when there is one, else its view's (k_ingest)
+  if (corr_tile_dark(K, D, pt_flags ? pt_flags + (int64_t)(D.list & 1) * K.pt_plane : dark, tail_flags, slot, oy0, ox0))
+    return;
   const int kh = D.kh, kwp = D.kwp, ch = D.chunk_rows;
   const int cols = LM_TW + kwp - 1, stride = pk_stride(cols);
   const int ew = K.ext_w[D.view];
@@ -1036,7 +1048,8 @@ __global__ __launch_bounds__(LM_F16_THREADS) __attribute__((amdgpu_waves_per_eu(
                                                             int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin,
                                                             int64_t tailbin_slot_bytes,
                                                             const uint8_t* __restrict__ dark,
-                                                            const uint8_t* __restrict__ /* tail flags: every tail tile is computed */) {
+                                                            const uint8_t* __restrict__ /* tail flags: every tail tile is computed */,
+                                                            const uint8_t* __restrict__ /* point flags: every bright tile is computed */) {
   const LmConst& K = *Kp;
   // uint4: the dynamic area starts 16-byte aligned after the static variables
   // (with a float array it would start 8 bytes in, and every ds_read_b128 of
@@ -1276,15 +1289,19 @@ hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t
   if (ring) {
     int nslots = (int)grid.y;
     const unsigned waves = (unsigned)(G.tile_end[G.n - 1] * nslots);  // every 80 x 16 tile (corr_locate_rw)
+    // a point detector's tiles: its own list (k_tile_bound) when there is one, else its view's (k_ingest)
+    int per_det = dk.pt_cnt != nullptr ? 1 : 0;
+    const int32_t* tl_cnt = per_det ? dk.pt_cnt : dk.cnt;
+    const uint32_t* tl_list = per_det ? dk.pt_list : dk.list;
     void* args[] = {(void*)&K,       (void*)&G,    (void*)&ext,     (void*)&ext_slot_bytes,
                     (void*)&weights, (void*)&s0,   (void*)&nslots,  (void*)&keys,
-                    (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes, (void*)&dk.cnt,
-                    (void*)&dk.list, (void*)&dk.tail_cnt, (void*)&dk.tail_list};
+                    (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes, (void*)&tl_cnt,
+                    (void*)&tl_list, (void*)&per_det, (void*)&dk.tail_cnt, (void*)&dk.tail_list};
     return hipLaunchKernel(fn, dim3((waves + LM_RW_WAVES - 1) / LM_RW_WAVES), dim3(LM_RW_THREADS), args, lds, st);
   }
   void* args[] = {(void*)&K,     (void*)&G,       (void*)&ext,     (void*)&ext_slot_bytes,           (void*)&weights,
                   (void*)&s0,    (void*)&keys,    (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes,
-                  (void*)&dk.flags, (void*)&dk.tail_flags};
+                  (void*)&dk.flags, (void*)&dk.tail_flags, (void*)&dk.pt_flags};
   return hipLaunchKernel(fn, grid, dim3(threads), args, lds, st);
 }
 

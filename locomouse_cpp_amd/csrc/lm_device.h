@@ -110,19 +110,30 @@ struct LmConst {
   // LM_TL_NC segments: segment c at lm_tl_y0(c, G) * LM_INGEST_FB * fl_tx * fl_ty
   int32_t fl_tx[2], fl_ty[2], fl_off[2], fl_slot;
   int32_t tl_stride;
-  // tail tiles (flagged and listed by k_tail_bound, lm_tail_bound.h): tail
+  // tail tiles (flagged and listed by k_tile_bound, lm_tail_bound.h): tail
   // detector t (0 bottom, 1 side) has tt_tx[t] x tt_ty[t] output tiles of
   // LM_FW x LM_FH; one flag byte per (slot, t, tile) at slot * tt_slot +
   // tt_off[t] + tile (1: not proven non-positive, to be computed); those
   // tiles listed at t * tt_stride of the tail tile list, in LM_TL_NC segments
   // like the point detectors' (segment c at lm_tl_y0(c, G) * LM_INGEST_FB *
-  // tt_tx * tt_ty).  tb_skip[t]: the bound may prove tiles (else every tile is
-  // listed); its P_i at tb_off[t], N_i at tb_off[t] + kh of the bound
-  // constants; tb_lds[t]: k_tail_bound's LDS bytes for the detector
+  // tt_tx * tt_ty).
   int32_t tt_tx[2], tt_ty[2], tt_off[2], tt_slot;
   int32_t tt_stride;
-  int32_t tb_skip[2], tb_off[2], tb_lds[2];
-  double tb_bias[2];
+  // point tiles (k_tile_bound): the bright tiles of point detector l (its
+  // list id) that are not proven non-positive, on the view's fl_tx x fl_ty
+  // grid; one flag byte per (feature l & 1, slot, view, tile) in k_ingest's
+  // layout, a plane of pt_plane bytes per feature (paw, snout): at
+  // (l & 1) * pt_plane + slot * fl_slot + fl_off[view] + tile; those tiles
+  // listed at l * tl_stride of the point tile list (the views' segment scheme
+  // and capacity)
+  int64_t pt_plane;
+  // the bound per detector d: tb_skip[d]: it may prove tiles (else every tile,
+  // of a point detector every bright tile, is listed); its P_i at tb_off[d],
+  // N_i at tb_off[d] + kh of the bound constants; tb_rng[d]: byte offset of
+  // the detector's row ranges in k_tile_bound's LDS (after the view's block
+  // ranges); tb_lds[v]: the kernel's LDS bytes for view v
+  int32_t tb_skip[LM_NDET], tb_off[LM_NDET], tb_rng[LM_NDET], tb_lds[2];
+  double tb_bias[LM_NDET];
   // the point detectors' output region per view: output (y, x) has its
   // I_*_MOUSE pixel at ext (fl_my + y, fl_mx + x); fl_oh x fl_ow outputs
   int32_t fl_my[2], fl_mx[2], fl_oh[2], fl_ow[2];

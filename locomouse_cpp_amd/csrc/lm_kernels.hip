@@ -7,7 +7,7 @@
 //   k_ingest      calibration gather + flip + LUT (+ the in-place grey-level LUT of
 //                 transform_gray_values) -> extended padded crops (u8)
 //                 :1316-1327 (correctImage :1337-1406), cropBoundingBox :1408-1478
-//   k_tail_bound  the tail detectors' 40 x 4 tiles whose scores are not proven
+//   k_tile_bound  every detector's 40 x 4 tiles whose scores are not proven
 //                 negative (lm_tail_bound.h), listed and flagged for k_corr
 //   k_corr        all six filter2D detectors, fp32 row-major FMA chains, LDS-tiled;
 //                 epilogue: brightness mask + score>0 compaction / tail binarisation
@@ -636,106 +636,166 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
 #undef ING_PROF
 }
 
-// ------------------------------------------------------------ k_tail_bound
-// The tail detectors' tiles that have to be computed.  The pipeline uses only
-// the sign of a tail score, and k_ingest has zeroed the tail bitmaps, so a
-// LM_FW x LM_FH tile whose scores are all provably < 0 (lm_tail_bound.h: an
-// upper bound from per-row pixel ranges, with the fp32 chain's rounding error
-// added) is left out.  One workgroup per (slot, tail detector): the
-// detector's window of the ext crop ((oh + kh - 1) x (ow + kw - 1) bytes)
-// reduced to pixel ranges per row and block of 8 columns, those to ranges per
-// row and tile column, then the bound per tile; the tiles not proven are
-// flagged (one byte each, for k_corr_gen) and appended to the detector's list
-// segments (for the ring kernels), in the point detectors' entry format and
-// segment scheme (k_ingest).  A detector without a usable bound (tb_skip = 0:
-// rho <= 0, non-finite weights, a window beyond the LDS) lists every tile.
-static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the tail bound's tiles are the dark-tile grid's");
+// ------------------------------------------------------------ k_tile_bound
+// The tiles of a view's three detectors that the correlation has to compute.
+// The pipeline uses only the sign of a tail score (k_ingest has zeroed the
+// tail bitmaps) and of a point score only whether it is > 0 under a bright
+// mask pixel (corr_epilogue), so a LM_FW x LM_FH tile whose scores are all
+// provably < 0 (lm_tail_bound.h: an upper bound from per-row pixel ranges,
+// with the fp32 chain's rounding error added) is left out.  One workgroup per
+// (slot, view): the view's ext crop is read once and reduced to pixel ranges
+// per row and aligned block of 8 columns; from those, per detector (paw,
+// snout, tail: each with its own window origin, column spans and constants),
+// ranges per window row and tile column, then the bound per tile -- of a
+// point detector only for the tiles k_ingest flagged bright; a dark tile
+// stays unlisted without evaluation.  The tiles to compute are flagged (one
+// byte each, for k_corr_gen) and appended to the detector's own list segments
+// (for the ring kernels), in k_ingest's entry format and segment scheme.  A
+// detector without a usable bound (tb_skip = 0: rho <= 0, non-finite weights,
+// ranges beyond the LDS) lists every tile (a point detector: every bright
+// tile).  tt_cnt / pt_cnt null: the tail / point detectors are not handled
+// here (LM_CORR_TAILSKIP=0 / LM_CORR_POINTSKIP=0).
+static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the dark-tile grid's");
 #define LM_TB_THREADS 256
-__global__ __launch_bounds__(LM_TB_THREADS) void k_tail_bound(const LmConst* __restrict__ Kp,
-                                                              const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
-                                                              int s0, const double* __restrict__ tbc,
-                                                              uint8_t* __restrict__ flags, int32_t* __restrict__ tt_cnt,
-                                                              uint32_t* __restrict__ tt_list) {
+__global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound(
+    const LmConst* __restrict__ Kp, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes, int s0,
+    const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
+    int32_t* __restrict__ tt_cnt, uint32_t* __restrict__ tt_list, uint8_t* __restrict__ pt_flags,
+    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list) {
   const LmConst& K = *Kp;
   extern __shared__ uint8_t tb_lds[];
-  __shared__ int s_n, s_k, s_base;
-  const int t = (int)blockIdx.y, slot = s0 + (int)blockIdx.x;
+  __shared__ int s_n[3], s_b[3], s_k[3], s_base[3];
+  const int v = (int)blockIdx.y, slot = s0 + (int)blockIdx.x;
   const int T = (int)blockDim.x, tid = (int)threadIdx.x;
-  const LmDet& D = K.det[t ? DET_TAIL_S : DET_TAIL_B];
-  const int ftx = K.tt_tx[t], ntile = ftx * K.tt_ty[t];
-  uint8_t* __restrict__ fl = flags + (int64_t)slot * K.tt_slot + K.tt_off[t];
-  if (tid == 0) {
-    s_n = 0;
-    s_k = 0;
+  const int ew = K.ext_w[v], eh = K.ext_h[v], nbw = ew / LM_TB_BLK;  // (ext rows are multiples of 16 bytes)
+  uint8_t* bmax = tb_lds;
+  uint8_t* bmin = bmax + eh * nbw;
+  if (tid < 3) {
+    s_n[tid] = 0;
+    s_b[tid] = 0;
+    s_k[tid] = 0;
   }
-  if (K.tb_skip[t]) {
-    const int kh = D.kh, kw = D.kw, ew = K.ext_w[D.view];
-    const int rows = D.oh + kh - 1, wcols = D.ow + kw - 1, nblk = (wcols + LM_TB_BLK - 1) / LM_TB_BLK;
-    uint8_t* bmax = tb_lds;
-    uint8_t* bmin = bmax + rows * nblk;
-    uint8_t* rmax = bmin + rows * nblk;
-    uint8_t* rmin = rmax + rows * ftx;
-    const uint8_t* __restrict__ win = ext + (int64_t)slot * ext_slot_bytes +
-                                      (D.view ? (int64_t)K.ext_h[0] * K.ext_w[0] : 0) + (int64_t)D.in_y * ew + D.in_x;
+  // the view's detectors (paw, snout, tail: ids 3 v + k): on = its tiles are
+  // listed here, use = with the bound; the ext rows and blocks their windows span
+  static_assert(DET_PAW_S == 3 && DET_TAIL_B == 2 && DET_TAIL_S == 5, "three detectors per view, the tail last");
+  bool on[3], use[3];
+  int y_lo = eh, y_hi = 0, b_lo = nbw, b_hi = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const LmDet& D = K.det[3 * v + k];
+    on[k] = D.kind != 0 ? tt_cnt != nullptr : pt_cnt != nullptr;
+    use[k] = on[k] && K.tb_skip[3 * v + k] != 0;
+    if (use[k]) {  // (the host accepts a bound only when the window lies inside the ext crop)
+      y_lo = min(y_lo, D.in_y);
+      y_hi = max(y_hi, D.in_y + D.oh + D.kh - 1);
+      b_lo = min(b_lo, D.in_x / LM_TB_BLK);
+      b_hi = max(b_hi, (D.in_x + D.ow + D.kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK);
+    }
+  }
+  y_hi = min(y_hi, eh);
+  b_hi = min(b_hi, nbw);
+  if (y_lo < y_hi && b_lo < b_hi) {
+    const uint8_t* __restrict__ vsrc =
+        ext + (int64_t)slot * ext_slot_bytes + (v ? (int64_t)K.ext_h[0] * K.ext_w[0] : 0);
     static_assert(LM_TB_BLK == 8, "one 8-byte load per block");
-    // ranges per (row, block); a row's last block ends at the window's last
-    // column (the load may run a few bytes past it, inside the ext buffer)
-    // (batching eight of a thread's loads before their use changed nothing:
-    // 175 vs 178 us per launch among eight contexts' kernels, profiles/tailskip/)
-    for (int e = tid; e < rows * nblk; e += T) {
-      const int r = e / nblk, b = e - r * nblk;
-      uint2 v;
-      __builtin_memcpy(&v, win + (int64_t)r * ew + LM_TB_BLK * b, 8);
-      const int nv = min(LM_TB_BLK, wcols - LM_TB_BLK * b);
+    // ranges per (ext row, aligned block of 8 columns): every byte of the
+    // view read once, for all of its detectors
+    // (batching eight of a thread's loads before their use changed nothing for
+    // the tail detectors' pass: 175 vs 178 us per launch among eight contexts'
+    // kernels, profiles/tailskip/)
+    const int nb = b_hi - b_lo, ne = (y_hi - y_lo) * nb;
+    for (int e = tid; e < ne; e += T) {
+      const int r = y_lo + e / nb, b = b_lo + e % nb;
+      const uint2 p = *reinterpret_cast<const uint2*>(vsrc + (int64_t)r * ew + LM_TB_BLK * b);
       unsigned mx = 0u, mn = 255u;
 #pragma unroll
-      for (int k = 0; k < LM_TB_BLK; ++k) {
-        const unsigned p = ((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 0xFFu;
-        if (k < nv) {
-          mx = max(mx, p);
-          mn = min(mn, p);
-        }
+      for (int j = 0; j < LM_TB_BLK; ++j) {
+        const unsigned q = ((j < 4 ? p.x : p.y) >> (8 * (j & 3))) & 0xFFu;
+        mx = max(mx, q);
+        mn = min(mn, q);
       }
-      bmax[e] = (uint8_t)mx;
-      bmin[e] = (uint8_t)mn;
+      bmax[r * nbw + b] = (uint8_t)mx;
+      bmin[r * nbw + b] = (uint8_t)mn;
     }
-    __syncthreads();
-    // ranges per (row, tile column): the blocks of lm_tb_span's columns
+  }
+  __syncthreads();
+  // ranges per (detector, window row, tile column): the blocks that cover
+  // lm_tb_span's columns of the detector's window
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!use[k]) continue;
+    const LmDet& D = K.det[3 * v + k];
+    const int ftx = D.kind != 0 ? K.tt_tx[v] : K.fl_tx[v], rows = D.oh + D.kh - 1;
+    uint8_t* rmax = tb_lds + K.tb_rng[3 * v + k];
+    uint8_t* rmin = rmax + rows * ftx;
     for (int e = tid; e < rows * ftx; e += T) {
       const int r = e / ftx, tx = e - r * ftx;
-      int c0, c1;
-      lm_tb_span(tx, kw, D.ow, &c0, &c1);
+      int c0, c1, b0, b1;
+      lm_tb_span(tx, D.kw, D.ow, &c0, &c1);
+      lm_tb_blocks(D.in_x, c0, c1, &b0, &b1);
       unsigned mx = 0u, mn = 255u;
-      for (int b = c0 / LM_TB_BLK; b < (c1 + LM_TB_BLK - 1) / LM_TB_BLK; ++b) {
-        mx = max(mx, (unsigned)bmax[r * nblk + b]);
-        mn = min(mn, (unsigned)bmin[r * nblk + b]);
+      for (int b = b0; b < b1; ++b) {
+        mx = max(mx, (unsigned)bmax[(D.in_y + r) * nbw + b]);
+        mn = min(mn, (unsigned)bmin[(D.in_y + r) * nbw + b]);
       }
       rmax[e] = (uint8_t)mx;
       rmin[e] = (uint8_t)mn;
     }
-    __syncthreads();
-    const double* __restrict__ P = tbc + K.tb_off[t];
-    int mine = 0;
-    for (int i = tid; i < ntile; i += T) {
-      const bool skip = lm_tb_tile_skip(rmax, rmin, ftx, D.oh, kh, i / ftx, i % ftx, P, P + kh, K.tb_bias[t]);
-      fl[i] = skip ? 0 : 1;
-      mine += skip ? 0 : 1;
-    }
-    if (mine) atomicAdd(&s_n, mine);
-  } else {
-    for (int i = tid; i < ntile; i += T) fl[i] = 1;
-    if (tid == 0) s_n = ntile;
   }
   __syncthreads();
-  // this workgroup's list segment and its counter, as in k_ingest
+  // the flags: a tail tile unless proven, a point tile when k_ingest flagged
+  // it bright and it is not proven
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!on[k]) continue;
+    const int d = 3 * v + k;
+    const LmDet& D = K.det[d];
+    const bool tail = D.kind != 0;
+    const int ftx = tail ? K.tt_tx[v] : K.fl_tx[v], ntile = ftx * (tail ? K.tt_ty[v] : K.fl_ty[v]);
+    uint8_t* __restrict__ fl = tail ? tail_flags + (int64_t)slot * K.tt_slot + K.tt_off[v]
+                                    : pt_flags + (D.list & 1) * K.pt_plane + (int64_t)slot * K.fl_slot + K.fl_off[v];
+    const uint8_t* __restrict__ br = tail ? nullptr : bright + (int64_t)slot * K.fl_slot + K.fl_off[v];
+    const uint8_t* rmax = tb_lds + K.tb_rng[d];
+    const uint8_t* rmin = rmax + (D.oh + D.kh - 1) * ftx;
+    const double* __restrict__ P = tbc + K.tb_off[d];
+    int mine = 0, mbr = 0;
+    for (int i = tid; i < ntile; i += T) {
+      bool keep = br ? br[i] != 0 : true;
+      mbr += br && keep ? 1 : 0;
+      if (keep && use[k])
+        keep = !lm_tb_tile_skip(rmax, rmin, ftx, D.oh, D.kh, i / ftx, i % ftx, P, P + D.kh, K.tb_bias[d]);
+      fl[i] = keep ? 1 : 0;
+      mine += keep ? 1 : 0;
+    }
+    if (mine) atomicAdd(&s_n[k], mine);
+    if (mbr) atomicAdd(&s_b[k], mbr);
+  }
+  __syncthreads();
+  // this workgroup's list segments and their counters, as in k_ingest (a
+  // point detector's bright tiles counted next to its listed ones)
   const int G = ((int)gridDim.x + LM_INGEST_FB - 1) / LM_INGEST_FB;
   const int c = ((int)blockIdx.x / LM_INGEST_FB) * LM_TL_NC / G;
-  if (tid == 0) s_base = s_n ? atomicAdd(&tt_cnt[t * LM_TL_NC + c], s_n) : 0;
+  if (tid < 3 && (K.det[3 * v + tid].kind != 0 ? tt_cnt != nullptr : pt_cnt != nullptr)) {
+    const LmDet& D = K.det[3 * v + tid];
+    int32_t* __restrict__ cnt = D.kind != 0 ? tt_cnt + v * LM_TL_NC : pt_cnt + D.list * LM_TL_NC;
+    s_base[tid] = s_n[tid] ? atomicAdd(&cnt[c], s_n[tid]) : 0;
+    if (D.kind == 0 && s_b[tid]) atomicAdd(&pt_cnt[(LM_NLIST + D.list) * LM_TL_NC + c], s_b[tid]);
+  }
   __syncthreads();
-  uint32_t* __restrict__ out =
-      tt_list + (int64_t)t * K.tt_stride + (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base;
-  for (int i = tid; i < ntile; i += T)  // (each thread re-reads the flags it wrote)
-    if (fl[i]) out[atomicAdd(&s_k, 1)] = ((uint32_t)slot << 16) | (uint32_t)i;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!on[k]) continue;
+    const LmDet& D = K.det[3 * v + k];
+    const bool tail = D.kind != 0;
+    const int ntile = tail ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
+    const uint8_t* __restrict__ fl = tail ? tail_flags + (int64_t)slot * K.tt_slot + K.tt_off[v]
+                                          : pt_flags + (D.list & 1) * K.pt_plane + (int64_t)slot * K.fl_slot + K.fl_off[v];
+    uint32_t* __restrict__ out =
+        (tail ? tt_list + (int64_t)v * K.tt_stride : pt_list + (int64_t)D.list * K.tl_stride) +
+        (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
+    for (int i = tid; i < ntile; i += T)  // (each thread re-reads the flags it wrote)
+      if (fl[i]) out[atomicAdd(&s_k[k], 1)] = ((uint32_t)slot << 16) | (uint32_t)i;
+  }
 }
 
 #include "lm_corr.h"  // the correlation kernels are their own translation unit (lm_corr.hip)
@@ -2560,7 +2620,7 @@ DEV void carry_block(const LmConst& K, unsigned long long* __restrict__ keys, co
 //
 // k_prep: slots, frame pointers and the arena control block from host memory,
 // candidate counters and error flags zeroed.  One block.
-static_assert(4 * LM_TL_NC == 256, "k_prep zeroes the tile-list counters with its 256 threads");
+static_assert(4 * LM_TL_NC == 256 && 2 * LM_NLIST * LM_TL_NC == 512, "k_prep zeroes the tile-list counters with its 256 threads");
 __global__ __launch_bounds__(256) void k_prep(const LmSlot* __restrict__ h_slots, const uint8_t* const* __restrict__ h_fptr,
                                               const LmArenaCtl* __restrict__ h_ctl, int ns, LmSlot* __restrict__ slots,
                                               const uint8_t** __restrict__ fptr, LmArenaCtl* __restrict__ ctl,
@@ -2568,13 +2628,17 @@ __global__ __launch_bounds__(256) void k_prep(const LmSlot* __restrict__ h_slots
                                               const LmConst* __restrict__ Kp, unsigned long long* __restrict__ keys,
                                               const LmSlotOut* __restrict__ prev_hdr, int prev_slot,
                                               LmSlotOut* __restrict__ hdr, int32_t* __restrict__ dark_cnt,
-                                              int32_t* __restrict__ tail_cnt) {
+                                              int32_t* __restrict__ tail_cnt, int32_t* __restrict__ pt_cnt) {
   if (blockIdx.x == 1) {
     carry_block(*Kp, keys, prev_hdr, prev_slot, hdr);
     return;
   }
   if (dark_cnt) dark_cnt[threadIdx.x] = 0;  // k_ingest's bright-tile counters (4 LM_TL_NC = blockDim.x)
-  if (tail_cnt && threadIdx.x < 2 * LM_TL_NC) tail_cnt[threadIdx.x] = 0;  // k_tail_bound's tail-tile counters
+  if (tail_cnt && threadIdx.x < 2 * LM_TL_NC) tail_cnt[threadIdx.x] = 0;  // k_tile_bound's tail-tile counters
+  if (pt_cnt) {  // and its point-tile counters (listed and bright tiles per detector)
+    pt_cnt[threadIdx.x] = 0;
+    pt_cnt[256 + threadIdx.x] = 0;
+  }
   for (int i = threadIdx.x; i < ns; i += blockDim.x) {
     slots[i] = h_slots[i];
     fptr[i] = h_fptr[i];

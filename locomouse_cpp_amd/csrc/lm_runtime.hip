@@ -107,9 +107,12 @@ struct Lane {
   DevBuf<uint8_t> dark_flags;  // dark tiles (CorrDark): flag bytes, bright-tile lists and counts
   DevBuf<uint32_t> dark_list;
   DevBuf<int32_t> dark_cnt;
-  DevBuf<uint8_t> tail_flags;  // tail tiles not proven non-positive (k_tail_bound): flag bytes, lists and counts
+  DevBuf<uint8_t> tail_flags;  // tail tiles not proven non-positive (k_tile_bound): flag bytes, lists and counts
   DevBuf<uint32_t> tail_list;
   DevBuf<int32_t> tail_cnt;
+  DevBuf<uint8_t> pt_flags;  // per point detector: bright tiles not proven non-positive (k_tile_bound)
+  DevBuf<uint32_t> pt_list;
+  DevBuf<int32_t> pt_cnt;    // per list id 64 segment counters of listed tiles, then of bright tiles
   HostBuf<int32_t> h_cnt;   // debug bit 1: dark_cnt of the submitted batch, copied on its stream
   bool h_cnt_valid = false;
   DevBuf<long long> kprof;  // LM_KPROF=1: kernel phase timestamps
@@ -215,7 +218,11 @@ struct lm_ctx {
   // skip the tail detectors' tiles that lm_tail_bound.h proves non-positive
   // (LM_CORR_TAILSKIP=0: compute every tail tile; never in the f16 mode)
   bool tailskip_on = true;
-  DevBuf<double> tb_const;  // the bound's P_i, N_i per tail detector (LmConst::tb_off)
+  // the same for the point detectors' bright tiles (LM_CORR_POINTSKIP=0:
+  // compute every bright tile; never in the f16 mode or with LM_CORR_DARK=0)
+  bool pointskip_on = true;
+  size_t tb_lds = 0;        // k_tile_bound's LDS bytes (the larger view's)
+  DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off)
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
   DevBuf<uint8_t> handoff;     // two frames: the last frame of submitted batch k in slot k & 1
@@ -696,7 +703,9 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   // bound's constants (lm_tail_bound.h) from the fp32 weights the kernels use
   std::vector<double> tbc;
   if (const char* v = getenv("LM_CORR_TAILSKIP")) c->tailskip_on = atoi(v) != 0;
-  if (su->corr_precision == LM_CORR_F16) c->tailskip_on = false;
+  if (const char* v = getenv("LM_CORR_POINTSKIP")) c->pointskip_on = atoi(v) != 0;
+  if (su->corr_precision == LM_CORR_F16) c->tailskip_on = c->pointskip_on = false;  // the bound is for the fp32 chain
+  if (!c->dark_on) c->pointskip_on = false;  // it starts from k_ingest's bright flags
   {
     int o = 0, mt = 0;
     for (int t = 0; t < 2; ++t) {
@@ -706,20 +715,41 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
       K.tt_off[t] = o;
       o += (K.tt_tx[t] * K.tt_ty[t] + 3) / 4 * 4;
       mt = std::max(mt, K.tt_tx[t] * K.tt_ty[t]);
-      K.tb_off[t] = (int32_t)tbc.size();
-      tbc.resize(tbc.size() + 2 * (size_t)D.kh);
-      K.tb_skip[t] = lm_tb_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.delta, tbc.data() + K.tb_off[t],
-                                   tbc.data() + K.tb_off[t] + D.kh, &K.tb_bias[t]);
-      // k_tail_bound's pixel ranges of the detector's window, in LDS
-      const int64_t rows = (int64_t)D.oh + D.kh - 1, nblk = (D.ow + D.kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK;
-      const int64_t lds = 2 * rows * (nblk + K.tt_tx[t]);
-      if (lds > 64 * 1024) K.tb_skip[t] = 0;
-      K.tb_lds[t] = K.tb_skip[t] ? (int32_t)lds : 0;
     }
     K.tt_slot = o;
     K.tt_stride = c->nslots * mt;
     // (list entries hold slot << 16 | tile)
     if (mt > 65535 || c->nslots > 65535) c->tailskip_on = false;
+    // the point detectors' own flags: k_ingest's layout once per feature (lists: tl_stride each)
+    static_assert(LIST_PAW_B == 0 && LIST_SNOUT_B == 1 && LIST_PAW_S == 2 && LIST_SNOUT_S == 3, "list l: feature l & 1");
+    K.pt_plane = (int64_t)K.fl_slot * c->nslots;
+    if (K.fl_tx[0] * K.fl_ty[0] > 65535 || K.fl_tx[1] * K.fl_ty[1] > 65535 || c->nslots > 65535) c->pointskip_on = false;
+    // the bound's constants per detector and k_tile_bound's LDS per view: the
+    // view's block ranges, then the row ranges of each detector whose bound is
+    // usable and fits (the tail detector first)
+    constexpr int64_t kTileBoundLds = 144 * 1024;
+    for (int v = 0; v < 2; ++v) {
+      int64_t lds = 2 * (int64_t)K.ext_h[v] * (K.ext_w[v] / LM_TB_BLK);
+      bool any = false;
+      for (int d : {3 * v + 2, 3 * v, 3 * v + 1}) {
+        const LmDet& D = K.det[d];
+        K.tb_off[d] = (int32_t)tbc.size();
+        tbc.resize(tbc.size() + 2 * (size_t)D.kh);
+        K.tb_skip[d] = lm_tb_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.delta, tbc.data() + K.tb_off[d],
+                                     tbc.data() + K.tb_off[d] + D.kh, &K.tb_bias[d]);
+        const int64_t rows = (int64_t)D.oh + D.kh - 1, wcols = (int64_t)D.ow + D.kw - 1;
+        const int64_t need = 2 * rows * (D.kind != 0 ? K.tt_tx[v] : K.fl_tx[v]);
+        const bool inside = D.in_y >= 0 && D.in_x >= 0 && D.in_y + rows <= K.ext_h[v] && D.in_x + wcols <= K.ext_w[v];
+        if (!(D.kind != 0 ? c->tailskip_on : c->pointskip_on) || !inside || lds + need > kTileBoundLds) K.tb_skip[d] = 0;
+        K.tb_rng[d] = K.tb_skip[d] ? (int32_t)lds : 0;
+        if (K.tb_skip[d]) {
+          lds += need;
+          any = true;
+        }
+      }
+      K.tb_lds[v] = any ? (int32_t)lds : 0;
+      c->tb_lds = std::max(c->tb_lds, (size_t)K.tb_lds[v]);
+    }
   }
   // LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
   // scaled by 2^s so that the largest |w| lands in [2^14, 2^15) (the rounding
@@ -785,6 +815,7 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   COPY_SYNC(c->dK.p, &c->K, sizeof(LmConst), hipMemcpyHostToDevice, cs);
   c->fstride = (nv + 255) / 256 * 256;
   HIPCHK(hipFuncSetAttribute((const void*)k_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tail_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tb_lds));
   for (const auto& P : c->corr_plan)
     for (size_t g = 0; g < P.groups.size(); ++g)
       HIPCHK(hipFuncSetAttribute(P.groups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds[g]));
@@ -833,6 +864,13 @@ void lane_alloc(lm_ctx* c, Lane& L) {
     L.tail_list.alloc((size_t)2 * K.tt_stride);
     L.tail_cnt.alloc(2 * LM_TL_NC);
     SET_SYNC(L.tail_cnt.p, 0, 2 * LM_TL_NC * sizeof(int32_t), st);
+  }
+  if (c->pointskip_on) {
+    L.pt_flags.alloc((size_t)2 * K.pt_plane);
+    SET_SYNC(L.pt_flags.p, 0, (size_t)2 * K.pt_plane, st);
+    L.pt_list.alloc((size_t)LM_NLIST * K.tl_stride);
+    L.pt_cnt.alloc(2 * LM_NLIST * LM_TL_NC);
+    SET_SYNC(L.pt_cnt.p, 0, 2 * LM_NLIST * LM_TL_NC * sizeof(int32_t), st);
   }
   L.err.alloc(16);
   L.frame_ptr.alloc(ns);
@@ -1138,6 +1176,11 @@ CorrDark lane_dark(const lm_ctx* c, Lane& L) {
     d.tail_cnt = L.tail_cnt.p;
     d.tail_list = L.tail_list.p;
   }
+  if (c->pointskip_on) {
+    d.pt_flags = L.pt_flags.p;
+    d.pt_cnt = L.pt_cnt.p;
+    d.pt_list = L.pt_list.p;
+  }
   return d;
 }
 
@@ -1156,7 +1199,7 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
     // block 1: k_carry (a rerun keeps slot 0's staged candidates)
     k_prep<<<do_carry ? 2 : 1, 256, 0, st>>>(L.h_slots.d, L.h_frame_ptr.d, L.h_ctl.d, n + 1, L.slots.p, L.frame_ptr.p,
                                              A.ctl.p, L.npos.p, L.err.p, dK, L.keys.p, L.arena[P.prv].hdr.p, P.last_n,
-                                             A.hdr.p, L.dark_cnt.p, L.tail_cnt.p);
+                                             A.hdr.p, L.dark_cnt.p, L.tail_cnt.p, L.pt_cnt.p);
     T.begin("k_minmax");
     k_minmax<<<dim3(LM_MM_SPLIT, n + 1 - s_lut0), LM_MM_THREADS, 0, st>>>(L.frame_ptr.p, c->bkg.p, c->npix, s_lut0,
                                                                         L.mm.p);
@@ -1177,10 +1220,11 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
                                         c->ext_slot_bytes, reinterpret_cast<unsigned*>(L.tailbin.p), L.smap.p, L.sbkg.p,
                                         L.skey.p, dk.flags, dk.cnt, dk.list, kpi);
     T.end();
-    if (dk.tail_cnt) {  // the tail detectors' tiles that the correlation has to compute
-      T.begin("k_tail_bound");
-      k_tail_bound<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, (size_t)std::max(K.tb_lds[0], K.tb_lds[1]), st>>>(
-          dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.tail_flags, dk.tail_cnt, dk.tail_list);
+    if (dk.tail_cnt || dk.pt_cnt) {  // the tiles that the correlation has to compute, per detector
+      T.begin("k_tile_bound");
+      k_tile_bound<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, c->tb_lds, st>>>(
+          dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.flags, dk.tail_flags, dk.tail_cnt, dk.tail_list,
+          dk.pt_flags, dk.pt_cnt, dk.pt_list);
       T.end();
     }
   }
@@ -1961,6 +2005,41 @@ LM_API lm_status lm_debug_tail_tiles(lm_ctx* ctx, int32_t f, int32_t view, uint8
     HIPCHK(hipSetDevice(ctx->device));
     COPY_SYNC(out, L.tail_flags.p + (int64_t)(f + 1) * ctx->K.tt_slot + ctx->K.tt_off[view], (size_t)rows * cols,
               hipMemcpyDeviceToHost, L.stream);
+  });
+}
+
+LM_API lm_status lm_debug_point_work(lm_ctx* ctx, int32_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  for (int k = 0; k < 2 * LM_NLIST; ++k) out[k] = -1;
+  if (!ctx->pointskip_on) return LM_OK;
+  const Lane* Lp = delivered_lane(ctx);
+  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
+  const Lane& L = *Lp;
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t h[2 * LM_NLIST * LM_TL_NC];
+    COPY_SYNC(h, L.pt_cnt.p, sizeof(h), hipMemcpyDeviceToHost, L.stream);
+    for (int l = 0; l < LM_NLIST; ++l) {
+      out[2 * l] = std::accumulate(h + l * LM_TL_NC, h + (l + 1) * LM_TL_NC, 0);
+      out[2 * l + 1] = std::accumulate(h + (LM_NLIST + l) * LM_TL_NC, h + (LM_NLIST + l + 1) * LM_TL_NC, 0);
+    }
+  });
+}
+
+LM_API lm_status lm_debug_point_tiles(lm_ctx* ctx, int32_t f, int32_t det, uint8_t* out, int32_t rows, int32_t cols) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (!ctx->pointskip_on) return fail(LM_ERR_INVALID_ARGUMENT, "point-tile skipping is off");
+  const Lane* Lp = delivered_lane(ctx);
+  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
+  const Lane& L = *Lp;
+  if (f < 0 || f >= L.batch_n || det < 0 || det >= LM_NDET || ctx->K.det[det].kind != 0)
+    return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
+  const int view = ctx->K.det[det].view, list = ctx->K.det[det].list;
+  if (rows != ctx->K.fl_ty[view] || cols != ctx->K.fl_tx[view]) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    COPY_SYNC(out, L.pt_flags.p + (list & 1) * ctx->K.pt_plane + (int64_t)(f + 1) * ctx->K.fl_slot + ctx->K.fl_off[view],
+              (size_t)rows * cols, hipMemcpyDeviceToHost, L.stream);
   });
 }
 

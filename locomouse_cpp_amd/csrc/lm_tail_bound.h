@@ -1,11 +1,21 @@
 /*
- * lm_tail_bound.h — an upper bound on a tail detector's scores over one
- * 40 x 4 output tile, from per-row pixel ranges (plain C++: the host runtime,
- * the k_tail_bound kernel and tests/cpp/tail_bound_check.cpp share it).
+ * lm_tail_bound.h — an upper bound on a detector's scores over one 40 x 4
+ * output tile, from per-row pixel ranges (plain C++: the host runtime, the
+ * k_tile_bound kernel, tests/cpp/tail_bound_check.cpp and
+ * tests/cpp/point_bound_check.cpp share it).  Written for the tail
+ * detectors (hence the name); it serves the point detectors too.
  *
  * The pipeline uses only the sign of a tail score (threshold(> 0), then
  * connected components), and k_ingest zeroes the tail bitmaps, so a tile
  * whose scores are all provably < 0 need not be computed.
+ *
+ * A point detector's score (paw, snout) is kept only when its mouse pixel is
+ * > 25 and the score itself is > 0 (corr_epilogue, lm_corr.hip: the key list
+ * takes nothing else), and everything else about it is discarded.  A tile
+ * whose scores are all provably < 0 therefore appends no key, whatever its
+ * mask pixels are, exactly as a dark tile appends none: the same predicate is
+ * sufficient, with the same rounding margin, since the point detectors run
+ * the same fp32 chain.
  *
  * The detector: fp32 weights w[i][j] (kh x kw), start value delta, score
  *     s(y, x) = delta + sum_ij w[i][j] I(y + i, x + j)
@@ -85,6 +95,17 @@ LM_TB_HD inline void lm_tb_span(int tx, int kw, int ow, int* c0, int* c1) {
   const int end = (x1 - 1 + kw + LM_TB_BLK - 1) / LM_TB_BLK * LM_TB_BLK;
   *c0 = tx * LM_TB_W;
   *c1 = end < ow + kw - 1 ? end : ow + kw - 1;
+}
+
+// The aligned blocks [b0, b1) of LM_TB_BLK view columns that cover window
+// columns [c0, c1) of a window whose column 0 is view column x0 >= 0.
+// k_tile_bound reduces a view once to pixel ranges per such block for all of
+// its detectors, whose windows start at different columns; a detector's span
+// is then widened to whole blocks (by < LM_TB_BLK pixels of the same crop row
+// on either side), which only weakens the bound.
+LM_TB_HD inline void lm_tb_blocks(int x0, int c0, int c1, int* b0, int* b1) {
+  *b0 = (x0 + c0) / LM_TB_BLK;
+  *b1 = (x0 + c1 + LM_TB_BLK - 1) / LM_TB_BLK;
 }
 
 // Largest and smallest pixel of row[c0 .. c1 - 1].

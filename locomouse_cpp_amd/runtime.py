@@ -26,7 +26,8 @@ EXPORTED = (
     "lm_bb_stream", "lm_host_alloc", "lm_host_free",
     "lm_detect_submit", "lm_detect_submit_device", "lm_detect_collect", "lm_ctx_lanes", "lm_ctx_pending",
     "lm_debug_corr_work", "lm_debug_batch_slots", "lm_debug_dark_tile_width",
-    "lm_debug_dark_tile_height", "lm_debug_tail_work", "lm_debug_tail_tiles",
+    "lm_debug_dark_tile_height", "lm_debug_tail_work", "lm_debug_tail_tiles", "lm_debug_point_work",
+    "lm_debug_point_tiles",
 )
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -177,6 +178,8 @@ def lib():
         L.lm_debug_corr_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.lm_debug_tail_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.lm_debug_tail_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+        L.lm_debug_point_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.lm_debug_point_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
         L.lm_debug_batch_slots.argtypes = [C.c_void_p]
         L.lm_debug_batch_slots.restype = C.c_int32
         L.lm_synth_frames_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
@@ -391,6 +394,25 @@ class Context:
         oh = (g.bb_side_mouse if view else g.bb_bottom_mouse).height
         out = np.zeros((-(-oh // th), -(-g.tail_box_width // tw)), dtype=np.uint8)
         _check(lib().lm_debug_tail_tiles(self._h, f, view, out.ctypes.data, out.shape[0], out.shape[1]))
+        return out
+
+    def point_work(self):
+        """Tiles listed for computing and bright tiles of the last batch, for
+        paw_bottom, snout_bottom, paw_side, snout_side (lm_debug_point_work),
+        or None with the skip off."""
+        out = (C.c_int32 * 8)()
+        _check(lib().lm_debug_point_work(self._h, out))
+        return None if out[0] < 0 else {"listed": tuple(out[0:8:2]), "bright": tuple(out[1:8:2])}
+
+    def point_tiles(self, f, det):
+        """[tile rows, tile columns] u8: 1 where frame f's tile of point
+        detector `det` (0 paw_bottom, 1 snout_bottom, 3 paw_side, 4
+        snout_side) was listed (lm_debug_point_tiles)."""
+        g = self.geometry()
+        tw, th = self.dark_tile_shape()
+        box = g.bb_side_mouse if det >= 3 else g.bb_bottom_mouse
+        out = np.zeros((-(-box.height // th), -(-box.width // tw)), dtype=np.uint8)
+        _check(lib().lm_debug_point_tiles(self._h, f, det, out.ctypes.data, out.shape[0], out.shape[1]))
         return out
 
     def batch_slots(self):
