@@ -134,6 +134,21 @@ struct LmConst {
   // ranges); tb_lds[v]: the kernel's LDS bytes for view v
   int32_t tb_skip[LM_NDET], tb_off[LM_NDET], tb_rng[LM_NDET], tb_lds[2];
   double tb_bias[LM_NDET];
+  // k_tile_bound (the banded kernel that reads k_ingest's block ranges; the
+  // tb_rng / tb_lds above are k_tile_bound_ref's).  View v is split into
+  // tbw_nband[v] bands of tbw_br[v] tile rows of each of its detectors' grids.
+  // tbw_use[d]: detector d's bound is used (tb_skip[d], and its band tables
+  // fit the LDS); tbw_inv[d]: lm_rcp of its tile columns.  The band's LDS:
+  // block ranges (u16 max | min << 8 per ext row and block of the columns
+  // tbw_blo[v] .. + tbw_nbk[v], both even; at most tbw_rows[v] rows) at 0,
+  // their four-row windows at tbw_v[v]; per detector P_i and N_i at
+  // tbw_pn[d], the window table (lm_tail_bound.h: wmax, then wmin at +
+  // tbw_wsz[d]) at tbw_win[d], the list entries of the band at tbw_ent[d];
+  // the tiles to evaluate at tbw_work[v].  All byte offsets; tbw_lds[v] bytes
+  // in all.
+  int32_t tbw_br[2], tbw_nband[2], tbw_blo[2], tbw_nbk[2], tbw_rows[2], tbw_v[2], tbw_work[2], tbw_lds[2];
+  int32_t tbw_use[LM_NDET], tbw_pn[LM_NDET], tbw_win[LM_NDET], tbw_wsz[LM_NDET], tbw_ent[LM_NDET];
+  uint32_t tbw_inv[LM_NDET];
   // the point detectors' output region per view: output (y, x) has its
   // I_*_MOUSE pixel at ext (fl_my + y, fl_mx + x); fl_oh x fl_ow outputs
   int32_t fl_my[2], fl_mx[2], fl_oh[2], fl_ow[2];
@@ -163,6 +178,23 @@ struct LmConst {
   int32_t gray_lut_on;
   uint8_t gray_lut[256];
 };
+
+// x / d without a division, for x >= 0 and x d < 2^31: lm_div(x, lm_rcp(d))
+// (lm_rcp(d) = floor(2^31 / d) + 1 = (2^31 + e) / d with 0 < e <= d, so the
+// product exceeds x / d by x e / (d 2^31) < 1 / d)
+__host__ __device__ inline uint32_t lm_rcp(int d) { return (uint32_t)(0x80000000u / (uint32_t)d + 1u); }
+__host__ __device__ inline int lm_div(int x, uint32_t rcp) { return (int)(((uint64_t)(uint32_t)x * rcp) >> 31); }
+
+// k_tile_bound's band j of br tile rows, for a detector with ty tile rows:
+// its first tile row *t0, its tile rows *nty (0: the detector ends above the
+// band) and the output rows inside them (returned)
+__host__ __device__ inline int lm_tbw_band(const LmDet& D, int ty, int br, int j, int* t0, int* nty) {
+  *t0 = j * br;
+  const int t1 = ty < *t0 + br ? ty : *t0 + br;
+  *nty = t1 > *t0 ? t1 - *t0 : 0;
+  if (*nty == 0) return 0;
+  return (D.oh < LM_FH * t1 ? D.oh : LM_FH * t1) - LM_FH * *t0;
+}
 
 // per-slot frame info (uploaded per batch)
 struct LmSlot {

@@ -6,9 +6,11 @@
 //                 LocoMouse_class.cpp:1304-1310, TM.cpp:247, :3204-3242
 //   k_ingest      calibration gather + flip + LUT (+ the in-place grey-level LUT of
 //                 transform_gray_values) -> extended padded crops (u8)
-//                 :1316-1327 (correctImage :1337-1406), cropBoundingBox :1408-1478
+//                 :1316-1327 (correctImage :1337-1406), cropBoundingBox :1408-1478;
+//                 with them the pixel range of every aligned block of 8 columns
 //   k_tile_bound  every detector's 40 x 4 tiles whose scores are not proven
-//                 negative (lm_tail_bound.h), listed and flagged for k_corr
+//                 negative (lm_tail_bound.h, from those ranges), listed and
+//                 flagged for k_corr (k_tile_bound_ref: from the crops)
 //   k_corr        all six filter2D detectors, fp32 row-major FMA chains, LDS-tiled;
 //                 epilogue: brightness mask + score>0 compaction / tail binarisation
 //                 :845, :860, :2575-2576, :782, :817, :849, :864, :2593-2598
@@ -308,6 +310,20 @@ DEV uint32_t bright_bytes(uint32_t w) {
 // 0x80 in byte i of the result for bit i of the 4-bit n
 DEV uint32_t byte_mask4(uint32_t n) { return ((n * 0x00204081u) & 0x01010101u) << 7; }
 
+// Largest byte | smallest byte << 8 of the eight bytes of a, b: the pixel range
+// of an aligned block of LM_TB_BLK columns (lm_tail_bound.h).
+static_assert(LM_TB_BLK == 8 && LM_INGEST_VEC == 2 * LM_TB_BLK, "a 16-byte chunk holds two blocks");
+DEV uint32_t block_range(uint32_t a, uint32_t b) {
+  uint32_t mx = 0u, mn = 255u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t x = (a >> (8 * j)) & 0xFFu, y = (b >> (8 * j)) & 0xFFu;
+    mx = max(mx, max(x, y));
+    mn = min(mn, min(x, y));
+  }
+  return mx | mn << 8;
+}
+
 // The five aligned dwords that cover the 16 source bytes [lo, lo + 16) of a
 // run: one dwordx4 (gfx950 global loads need only dword alignment) plus one
 // dword -- two vector-memory instructions instead of five.
@@ -343,7 +359,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
                                                  unsigned* __restrict__ tailbm, const int2* __restrict__ smap,
                                                  const uint4* __restrict__ sbkg, const int32_t* __restrict__ skey,
                                                  uint8_t* __restrict__ flags, int32_t* __restrict__ tl_cnt,
-                                                 uint32_t* __restrict__ tl_list, long long* __restrict__ prof) {
+                                                 uint32_t* __restrict__ tl_list, uint32_t* __restrict__ rng,
+                                                 long long* __restrict__ prof) {
   const LmConst& K = *Kp;
   // LM_KPROF=1: clock64() of thread 0 at the phase ends, wall clock at start / end
   long long* pb = prof ? prof + (int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;
@@ -512,6 +529,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
 #pragma unroll
       for (int j = 0; j < 4; ++j) word[j] &= byte_keep4((in_mask >> (4 * j)) & 0xFu);
       *reinterpret_cast<uint4*>(ext + (int64_t)(sb + f) * ext_slot_bytes + q) = make_uint4(word[0], word[1], word[2], word[3]);
+      // k_tile_bound's block ranges: largest and smallest byte of each aligned
+      // half of the chunk as stored (rng: a kernel argument, tested once per chunk)
+      if (rng)
+        rng[(int64_t)(sb + f) * (ext_slot_bytes / LM_INGEST_VEC) + q / LM_INGEST_VEC] =
+            block_range(word[0], word[1]) | block_range(word[2], word[3]) << 16;
       if (flag_chunk) {
         uint32_t ha = 0u, hb = 0u;
 #pragma unroll
@@ -655,9 +677,19 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
 // ranges beyond the LDS) lists every tile (a point detector: every bright
 // tile).  tt_cnt / pt_cnt null: the tail / point detectors are not handled
 // here (LM_CORR_TAILSKIP=0 / LM_CORR_POINTSKIP=0).
+//
+// k_tile_bound_ref is the first form of the pre-pass (LM_TILE_BOUND_REF=1):
+// it reads the crops themselves and reduces a whole view per workgroup.  It is
+// kept as the reference that k_tile_bound (below) is tested against.
 static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the dark-tile grid's");
 #define LM_TB_THREADS 256
-__global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound(
+#ifndef LM_TBW_TILES
+#define LM_TBW_TILES LM_TB_THREADS  // k_tile_bound: about this many tiles of a view's detectors per band
+#endif
+#ifndef LM_TBW_LD
+#define LM_TBW_LD 8  // k_tile_bound: a thread's loads of block ranges in flight
+#endif
+__global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
     const LmConst* __restrict__ Kp, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes, int s0,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
     int32_t* __restrict__ tt_cnt, uint32_t* __restrict__ tt_list, uint8_t* __restrict__ pt_flags,
@@ -795,6 +827,268 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound(
         (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
     for (int i = tid; i < ntile; i += T)  // (each thread re-reads the flags it wrote)
       if (fl[i]) out[atomicAdd(&s_k[k], 1)] = ((uint32_t)slot << 16) | (uint32_t)i;
+  }
+}
+
+// The pre-pass the pipeline runs.  It computes what k_tile_bound_ref computes
+// (the same flags, counters and sets of list entries) from k_ingest's block
+// ranges (rng: per slot and 16-byte chunk of the ext crops, largest | smallest
+// byte of each aligned half, block_range) instead of the crops, a quarter of
+// their bytes.  One workgroup per (slot, view, band of LmConst::tbw_br tile
+// rows): about a workgroup's threads of tiles over the view's detectors, and a
+// few KB of LDS, so that many workgroups share a compute unit.
+//   1. The bright point tiles and all tail tiles of the band are compacted
+//      into a work list (a dark point tile is flagged 0 and costs nothing
+//      more); the band's block ranges are loaded, several loads per thread in
+//      flight.
+//   2. Their four-row windows: the rows a tile's outputs read at one weight
+//      row, the same for all of the view's detectors.
+//   3. Per detector the window table of lm_tail_bound.h: entry (window row,
+//      tile column) is the range over the column's blocks (lm_tb_span,
+//      lm_tb_blocks) of the four-row windows -- of the block ranges themselves
+//      for the rows of a last tile row of fewer than four output rows.
+//   4. lm_tb_tile_skip_win per listed tile: kh pairs of bytes, the work list
+//      handed out densely.  Kept tiles take their place in the band's entries
+//      by a ballot and one LDS atomic per wave.
+//   5. One global atomic per (workgroup, detector) on the slot group's segment
+//      counter (the segment index comes from the slot and the batch's slot
+//      count nslot, so all bands of a slot append to one segment), then the
+//      entries are copied out.
+// No index of a loop is divided at run time (lm_div by reciprocals).
+DEV uint32_t range_merge(uint32_t a, uint32_t b) {  // of two words of block ranges: max of bytes 0, 2, min of bytes 1, 3
+  return max(a & 0xFFu, b & 0xFFu) | min(a & 0xFF00u, b & 0xFF00u) | max(a & 0xFF0000u, b & 0xFF0000u) |
+         min(a & 0xFF000000u, b & 0xFF000000u);
+}
+// The place of each lane with p set in the sequence counted by *ctr (LDS): one
+// atomic per wave.  To be called by whole waves.
+DEV int wave_append(bool p, int* ctr) {
+  const unsigned long long m = __ballot(p);
+  if (m == 0ull) return 0;
+  const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+  int base = 0;
+  if (p && rank == 0) base = atomicAdd(ctr, (int)__popcll(m));
+  return __shfl(base, __ffsll((long long)m) - 1) + rank;
+}
+#ifndef LM_TBW_WPE
+#define LM_TBW_WPE 8  // amdgpu_waves_per_eu minimum: <= 64 VGPRs, eight workgroups per compute unit
+#endif
+__global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(LM_TBW_WPE, 8))) void k_tile_bound(
+    const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
+    const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
+    int32_t* __restrict__ tt_cnt, uint32_t* __restrict__ tt_list, uint8_t* __restrict__ pt_flags,
+    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list) {
+  const LmConst& K = *Kp;
+  extern __shared__ __attribute__((aligned(16))) uint8_t tbw_lds[];
+  __shared__ int s_n[3], s_b[3], s_base[3], s_nw;
+  const int v = (int)blockIdx.y < K.tbw_nband[0] ? 0 : 1;
+  const int band = (int)blockIdx.y - (v ? K.tbw_nband[0] : 0);
+  const int slot = s0 + (int)blockIdx.x;
+  const int T = (int)blockDim.x, tid = (int)threadIdx.x;
+  if (tid < 3) {
+    s_n[tid] = 0;
+    s_b[tid] = 0;
+  }
+  if (tid == 0) s_nw = 0;
+  // the view's detectors (paw, snout, tail: ids 3 v + k) in this band: on =
+  // its tiles are listed here, use = with the bound; t0, nt: its first tile
+  // row and tile count, ohb: its output rows; y_lo .. y_hi: the ext rows the
+  // windows of the detectors with a bound span
+  bool on[3], use[3], tail[3];
+  int t0[3], nt[3], ohb[3], ftx[3], tbase[3];
+  uint8_t* fl[3];
+  int y_lo = K.ext_h[v], y_hi = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int d = 3 * v + k;
+    const LmDet& D = K.det[d];
+    tail[k] = D.kind != 0;
+    on[k] = tail[k] ? tt_cnt != nullptr : pt_cnt != nullptr;
+    use[k] = on[k] && K.tbw_use[d] != 0;
+    ftx[k] = tail[k] ? K.tt_tx[v] : K.fl_tx[v];
+    int nty;
+    ohb[k] = lm_tbw_band(D, tail[k] ? K.tt_ty[v] : K.fl_ty[v], K.tbw_br[v], band, &t0[k], &nty);
+    nt[k] = on[k] ? nty * ftx[k] : 0;
+    tbase[k] = t0[k] * ftx[k];  // the band's first tile of the detector's grid
+    fl[k] = tail[k] ? tail_flags + (int64_t)slot * K.tt_slot + K.tt_off[v]
+                    : pt_flags + (D.list & 1) * K.pt_plane + (int64_t)slot * K.fl_slot + K.fl_off[v];
+    use[k] = use[k] && nt[k] > 0;
+    if (use[k]) {  // (the host accepts a bound only when the window lies inside the ext crop)
+      y_lo = min(y_lo, D.in_y + LM_FH * t0[k]);
+      y_hi = max(y_hi, D.in_y + LM_FH * t0[k] + ohb[k] + D.kh - 1);
+    }
+  }
+  y_hi = min(y_hi, K.ext_h[v]);
+  const int nrow = max(0, min(y_hi - y_lo, K.tbw_rows[v]));
+  const int nbk = K.tbw_nbk[v], nw = nbk / 2;  // blocks and words (of two blocks) per row
+  uint32_t* B = reinterpret_cast<uint32_t*>(tbw_lds);
+  uint32_t* V = reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_v[v]);
+  uint32_t* work = reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_work[v]);
+  __syncthreads();
+  // The band's block ranges: LM_TBW_LD loads per thread in flight, the first
+  // round issued before the work list is built (whose loads of the bright
+  // flags then wait alongside them), P_i and N_i likewise.
+  constexpr int LD = LM_TBW_LD;
+  const int ne = nrow * nw, ewq = K.ext_w[v] / LM_INGEST_VEC;
+  const uint32_t rc = lm_rcp(max(nw, 1));
+  const uint32_t* __restrict__ src = rng + (int64_t)slot * rng_slot +
+                                     (v ? (int64_t)K.ext_h[0] * K.ext_w[0] / LM_INGEST_VEC : 0) +
+                                     (int64_t)min(y_lo, y_hi) * ewq + K.tbw_blo[v] / 2;
+  uint32_t w[LD];
+  auto rng_load = [&](int e0) {
+#pragma unroll
+    for (int u = 0; u < LD; ++u) {
+      const int e = e0 + u * T + tid;
+      if (e < ne) {
+        const int r = lm_div(e, rc);
+        w[u] = src[r * ewq + (e - r * nw)];
+      }
+    }
+  };
+  auto rng_store = [&](int e0) {
+#pragma unroll
+    for (int u = 0; u < LD; ++u) {
+      const int e = e0 + u * T + tid;
+      if (e < ne) B[e] = w[u];
+    }
+  };
+  rng_load(0);
+  double pnv[3] = {0.0, 0.0, 0.0};  // (a detector has at most T / 2 rows: the host checks)
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (use[k] && tid < 2 * K.det[3 * v + k].kh) pnv[k] = tbc[K.tb_off[3 * v + k] + tid];
+  // 1. the work list: tile j of the band of detector k as k << 28 | j
+  const uint8_t* __restrict__ br = bright + (int64_t)slot * K.fl_slot + K.fl_off[v];
+  const int ntot = nt[0] + nt[1] + nt[2];
+  for (int i0 = 0; i0 < ntot; i0 += T) {
+    const int i = i0 + tid;
+    const bool act = i < ntot;
+    const int k = i < nt[0] ? 0 : i < nt[0] + nt[1] ? 1 : 2;
+    const int j = i - (k == 0 ? 0 : k == 1 ? nt[0] : nt[0] + nt[1]);
+    const bool tl = k == 0 ? tail[0] : k == 1 ? tail[1] : tail[2];
+    const int tb = k == 0 ? tbase[0] : k == 1 ? tbase[1] : tbase[2];
+    bool cand = act;
+    if (act && !tl) {
+      cand = br[tb + j] != 0;
+      if (!cand) (k == 0 ? fl[0] : k == 1 ? fl[1] : fl[2])[tb + j] = 0;
+    }
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) {  // a point detector's bright tiles, counted next to its listed ones
+      const unsigned long long m = __ballot(cand && !tl && k == kk);
+      if (m != 0ull && (tid & 63) == 0) atomicAdd(&s_b[kk], (int)__popcll(m));
+    }
+    const int pos = wave_append(cand, &s_nw);
+    if (cand) work[pos] = (uint32_t)k << 28 | (uint32_t)j;
+  }
+  rng_store(0);
+  for (int e0 = LD * T; e0 < ne; e0 += LD * T) {
+    rng_load(e0);
+    rng_store(e0);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (use[k] && tid < 2 * K.det[3 * v + k].kh) reinterpret_cast<double*>(tbw_lds + K.tbw_pn[3 * v + k])[tid] = pnv[k];
+  __syncthreads();
+  // 2. four-row windows of the block ranges
+  for (int e = tid; e < (nrow - (LM_TB_H - 1)) * nw; e += T)
+    V[e] = range_merge(range_merge(B[e], B[e + nw]), range_merge(B[e + 2 * nw], B[e + 3 * nw]));
+  static_assert(LM_TB_H == 4, "four-row windows");
+  __syncthreads();
+  // 3. the detectors' window tables
+  const uint16_t* B16 = reinterpret_cast<const uint16_t*>(B);
+  const uint16_t* V16 = reinterpret_cast<const uint16_t*>(V);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!use[k]) continue;
+    const int d = 3 * v + k;
+    const LmDet& D = K.det[d];
+    uint8_t* wmax = tbw_lds + K.tbw_win[d];
+    uint8_t* wmin = wmax + K.tbw_wsz[d];
+    const int nent = min(lm_tb_win_rows(ohb[k], D.kh) * ftx[k], K.tbw_wsz[d]);
+    const uint32_t rc = K.tbw_inv[d];
+    const int yb = D.in_y + LM_FH * t0[k] - y_lo;  // the band's window row 0 among the loaded rows
+    for (int e = tid; e < nent; e += T) {
+      const int w = lm_div(e, rc), tx = e - w * ftx[k];
+      int r0, nr, c0, c1, b0, b1;
+      lm_tb_win_src(ohb[k], D.kh, w, &r0, &nr);
+      lm_tb_span(tx, D.kw, D.ow, &c0, &c1);
+      lm_tb_blocks(D.in_x, c0, c1, &b0, &b1);
+      b0 = max(b0 - K.tbw_blo[v], 0);
+      b1 = min(b1 - K.tbw_blo[v], nbk);
+      const uint16_t* row = (nr == LM_TB_H ? V16 : B16) + (yb + r0) * nbk;
+      const int nrr = nr == LM_TB_H ? 1 : nr;
+      unsigned mx = 0u, mn = 255u;
+      for (int r = 0; r < nrr; ++r, row += nbk)
+        for (int b = b0; b < b1; ++b) {
+          const unsigned q = row[b];
+          mx = max(mx, q & 0xFFu);
+          mn = min(mn, q >> 8);
+        }
+      wmax[e] = (uint8_t)mx;
+      wmin[e] = (uint8_t)mn;
+    }
+  }
+  __syncthreads();
+  // 4. the bound per tile of the work list
+  int kh3[3], win3[3], wsz3[3], pn3[3];
+  uint32_t inv3[3];
+  double bias3[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int d = 3 * v + k;
+    kh3[k] = K.det[d].kh;
+    win3[k] = K.tbw_win[d];
+    wsz3[k] = K.tbw_wsz[d];
+    pn3[k] = K.tbw_pn[d];
+    inv3[k] = K.tbw_inv[d];
+    bias3[k] = K.tb_bias[d];
+  }
+  const int nwork = s_nw;
+  for (int w0 = 0; w0 < nwork; w0 += T) {
+    const bool act = w0 + tid < nwork;
+    const uint32_t item = act ? work[w0 + tid] : 0u;
+    const int k = (int)(item >> 28), j = (int)(item & 0x0FFFFFFFu);
+    // (the detector's constants chosen among the three uniform sets, not loaded per lane)
+#define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
+    const int tb = TBW_SEL(tbase);
+    bool keep = act;
+    if (act && TBW_SEL(use)) {
+      const int fx = TBW_SEL(ftx), kh = TBW_SEL(kh3);
+      const int ty = lm_div(j, TBW_SEL(inv3)), tx = j - ty * fx;
+      const uint8_t* wmax = tbw_lds + TBW_SEL(win3);
+      const double* pn = reinterpret_cast<const double*>(tbw_lds + TBW_SEL(pn3));
+      keep = !lm_tb_tile_skip_win(wmax, wmax + TBW_SEL(wsz3), fx, kh, lm_tb_win_row0(TBW_SEL(ohb), kh, ty), tx, pn,
+                                  pn + kh, TBW_SEL(bias3));
+    }
+    if (act) TBW_SEL(fl)[tb + j] = keep ? 1 : 0;
+#undef TBW_SEL
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) {
+      const bool mine = act && keep && k == kk;
+      const int pos = wave_append(mine, &s_n[kk]);
+      if (mine) reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_ent[3 * v + kk])[pos] = ((uint32_t)slot << 16) | (uint32_t)(tb + j);
+    }
+  }
+  __syncthreads();
+  // 5. this workgroup's list segments and their counters, as in k_ingest
+  const int G = (nslot + LM_INGEST_FB - 1) / LM_INGEST_FB;
+  const int c = ((int)blockIdx.x / LM_INGEST_FB) * LM_TL_NC / G;
+  if (tid < 3 && (K.det[3 * v + tid].kind != 0 ? tt_cnt != nullptr : pt_cnt != nullptr)) {
+    const LmDet& D = K.det[3 * v + tid];
+    int32_t* __restrict__ cnt = D.kind != 0 ? tt_cnt + v * LM_TL_NC : pt_cnt + D.list * LM_TL_NC;
+    s_base[tid] = s_n[tid] ? atomicAdd(&cnt[c], s_n[tid]) : 0;
+    if (D.kind == 0 && s_b[tid]) atomicAdd(&pt_cnt[(LM_NLIST + D.list) * LM_TL_NC + c], s_b[tid]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!on[k] || s_n[k] == 0) continue;
+    const LmDet& D = K.det[3 * v + k];
+    const int ntile = tail[k] ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
+    const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + K.tbw_ent[3 * v + k]);
+    uint32_t* __restrict__ out =
+        (tail[k] ? tt_list + (int64_t)v * K.tt_stride : pt_list + (int64_t)D.list * K.tl_stride) +
+        (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
+    for (int p = tid; p < s_n[k]; p += T) out[p] = ent[p];
   }
 }
 

@@ -113,6 +113,7 @@ struct Lane {
   DevBuf<uint8_t> pt_flags;  // per point detector: bright tiles not proven non-positive (k_tile_bound)
   DevBuf<uint32_t> pt_list;
   DevBuf<int32_t> pt_cnt;    // per list id 64 segment counters of listed tiles, then of bright tiles
+  DevBuf<uint32_t> rng;      // k_ingest's block ranges for k_tile_bound: one word per 16-byte chunk of ext
   HostBuf<int32_t> h_cnt;   // debug bit 1: dark_cnt of the submitted batch, copied on its stream
   bool h_cnt_valid = false;
   DevBuf<long long> kprof;  // LM_KPROF=1: kernel phase timestamps
@@ -221,7 +222,11 @@ struct lm_ctx {
   // the same for the point detectors' bright tiles (LM_CORR_POINTSKIP=0:
   // compute every bright tile; never in the f16 mode or with LM_CORR_DARK=0)
   bool pointskip_on = true;
-  size_t tb_lds = 0;        // k_tile_bound's LDS bytes (the larger view's)
+  size_t tb_lds = 0;        // k_tile_bound_ref's LDS bytes (the larger view's)
+  size_t tbw_lds = 0;       // k_tile_bound's (the larger view's band)
+  // LM_TILE_BOUND_REF=1: the pre-pass is k_tile_bound_ref (it reads the crops;
+  // k_ingest then writes no block ranges)
+  bool tb_ref = false;
   DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off)
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
@@ -728,6 +733,7 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
     // view's block ranges, then the row ranges of each detector whose bound is
     // usable and fits (the tail detector first)
     constexpr int64_t kTileBoundLds = 144 * 1024;
+    constexpr int64_t kTileBoundWgLds = 64 * 1024;  // k_tile_bound's, per band
     for (int v = 0; v < 2; ++v) {
       int64_t lds = 2 * (int64_t)K.ext_h[v] * (K.ext_w[v] / LM_TB_BLK);
       bool any = false;
@@ -749,6 +755,107 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
       }
       K.tb_lds[v] = any ? (int32_t)lds : 0;
       c->tb_lds = std::max(c->tb_lds, (size_t)K.tb_lds[v]);
+    }
+    // k_tile_bound's bands (LmConst::tbw_*): tile rows per band so that the
+    // band's tiles over the view's detectors are about one workgroup's
+    // threads, evenly over the bands; the LDS of the largest band, with the
+    // same rule for what does not fit
+    if (const char* e = getenv("LM_TILE_BOUND_REF")) c->tb_ref = atoi(e) != 0;
+    for (int v = 0; v < 2; ++v) {
+      int ftx[3], ty[3], sum_tx = 0, max_ty = 1;
+      bool on[3];
+      for (int k = 0; k < 3; ++k) {
+        const LmDet& D = K.det[3 * v + k];
+        ftx[k] = D.kind != 0 ? K.tt_tx[v] : K.fl_tx[v];
+        ty[k] = D.kind != 0 ? K.tt_ty[v] : K.fl_ty[v];
+        on[k] = D.kind != 0 ? c->tailskip_on : c->pointskip_on;
+        if (on[k]) {
+          sum_tx += ftx[k];
+          max_ty = std::max(max_ty, ty[k]);
+        }
+      }
+      const int br0 = std::max(1, LM_TBW_TILES / std::max(1, sum_tx));
+      const int nband = (max_ty + br0 - 1) / br0, br = (max_ty + nband - 1) / nband;
+      K.tbw_br[v] = br;
+      K.tbw_nband[v] = (max_ty + br - 1) / br;
+      // the most window-table entries and ext rows of a band, for a set of detectors with a bound
+      auto band_rows = [&](const bool (&use)[3]) {
+        int rows = 0;
+        for (int j = 0; j < K.tbw_nband[v]; ++j) {
+          int y_lo = K.ext_h[v], y_hi = 0;
+          for (int k = 0; k < 3; ++k) {
+            const LmDet& D = K.det[3 * v + k];
+            int t0, nty;
+            const int ohb = lm_tbw_band(D, ty[k], br, j, &t0, &nty);
+            if (!use[k] || nty == 0) continue;
+            y_lo = std::min(y_lo, D.in_y + LM_FH * t0);
+            y_hi = std::max(y_hi, D.in_y + LM_FH * t0 + ohb + D.kh - 1);
+          }
+          rows = std::max(rows, std::min(y_hi, K.ext_h[v]) - y_lo);
+        }
+        return rows;
+      };
+      auto layout = [&](const bool (&use)[3]) {
+        int b_lo = K.ext_w[v] / LM_TB_BLK, b_hi = 0;
+        for (int k = 0; k < 3; ++k) {
+          const LmDet& D = K.det[3 * v + k];
+          if (!use[k]) continue;
+          b_lo = std::min(b_lo, D.in_x / LM_TB_BLK);
+          b_hi = std::max(b_hi, (D.in_x + D.ow + D.kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK);
+        }
+        b_lo = b_lo / 2 * 2;
+        b_hi = std::min((b_hi + 1) / 2 * 2, K.ext_w[v] / LM_TB_BLK);
+        K.tbw_blo[v] = b_lo < b_hi ? b_lo : 0;
+        K.tbw_nbk[v] = b_lo < b_hi ? b_hi - b_lo : 0;
+        K.tbw_rows[v] = std::max(0, band_rows(use));
+        int64_t o = 2 * (int64_t)K.tbw_rows[v] * K.tbw_nbk[v];
+        K.tbw_v[v] = (int32_t)o;
+        o += 2 * (int64_t)std::max(0, K.tbw_rows[v] - (LM_TB_H - 1)) * K.tbw_nbk[v];
+        o = (o + 7) / 8 * 8;
+        for (int k = 0; k < 3; ++k) {
+          const int d = 3 * v + k;
+          const LmDet& D = K.det[d];
+          K.tbw_use[d] = use[k] ? 1 : 0;
+          K.tbw_inv[d] = lm_rcp(ftx[k]);
+          K.tbw_pn[d] = (int32_t)o;
+          if (use[k]) o += 16 * (int64_t)D.kh;
+        }
+        for (int k = 0; k < 3; ++k) {
+          const int d = 3 * v + k;
+          const LmDet& D = K.det[d];
+          int wsz = 0;
+          for (int j = 0; use[k] && j < K.tbw_nband[v]; ++j) {
+            int t0, nty;
+            const int ohb = lm_tbw_band(D, ty[k], br, j, &t0, &nty);
+            if (nty) wsz = std::max(wsz, lm_tb_win_rows(ohb, D.kh) * ftx[k]);
+          }
+          K.tbw_win[d] = (int32_t)o;
+          K.tbw_wsz[d] = wsz;
+          o += 2 * (int64_t)wsz;
+        }
+        o = (o + 3) / 4 * 4;
+        for (int k = 0; k < 3; ++k) {
+          K.tbw_ent[3 * v + k] = (int32_t)o;
+          if (on[k]) o += 4 * (int64_t)br * ftx[k];
+        }
+        K.tbw_work[v] = (int32_t)o;
+        o += 4 * (int64_t)br * sum_tx;
+        return o;
+      };
+      // (the tail detector is the last to lose its bound, as in k_tile_bound_ref)
+      bool use[3];
+      // (a thread loads one of a detector's P_i, N_i: kh <= LM_TB_THREADS / 2)
+      for (int k = 0; k < 3; ++k)
+        use[k] = on[k] && K.tb_skip[3 * v + k] != 0 && 2 * K.det[3 * v + k].kh <= LM_TB_THREADS;
+      int64_t lds = layout(use);
+      for (int k : {1, 0, 2}) {
+        if (lds <= kTileBoundWgLds) break;
+        use[k] = false;
+        lds = layout(use);
+      }
+      if (lds > kTileBoundWgLds) throw std::invalid_argument("bounding box too wide for the tile lists' workgroup.");
+      K.tbw_lds[v] = (int32_t)lds;
+      c->tbw_lds = std::max(c->tbw_lds, (size_t)lds);
     }
   }
   // LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
@@ -815,7 +922,8 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   COPY_SYNC(c->dK.p, &c->K, sizeof(LmConst), hipMemcpyHostToDevice, cs);
   c->fstride = (nv + 255) / 256 * 256;
   HIPCHK(hipFuncSetAttribute((const void*)k_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tail_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tb_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound_ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tb_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
   for (const auto& P : c->corr_plan)
     for (size_t g = 0; g < P.groups.size(); ++g)
       HIPCHK(hipFuncSetAttribute(P.groups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds[g]));
@@ -871,6 +979,10 @@ void lane_alloc(lm_ctx* c, Lane& L) {
     L.pt_list.alloc((size_t)LM_NLIST * K.tl_stride);
     L.pt_cnt.alloc(2 * LM_NLIST * LM_TL_NC);
     SET_SYNC(L.pt_cnt.p, 0, 2 * LM_NLIST * LM_TL_NC * sizeof(int32_t), st);
+  }
+  if ((c->tailskip_on || c->pointskip_on) && !c->tb_ref) {
+    L.rng.alloc((size_t)(c->ext_slot_bytes / LM_INGEST_VEC) * ns);
+    SET_SYNC(L.rng.p, 0, (size_t)(c->ext_slot_bytes / LM_INGEST_VEC) * ns * sizeof(uint32_t), st);
   }
   L.err.alloc(16);
   L.frame_ptr.alloc(ns);
@@ -1218,13 +1330,18 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
     k_ingest<<<dim3((unsigned)(K.ing_nb[0] + K.ing_nb[1]), (unsigned)((nproc + LM_INGEST_FB - 1) / LM_INGEST_FB)),
                K.ing_threads, 0, st>>>(dK, L.frame_ptr.p, c->bkg.p, c->cal.p, L.luts.p, L.slots.p, s_proc0, n + 1, L.ext.p,
                                         c->ext_slot_bytes, reinterpret_cast<unsigned*>(L.tailbin.p), L.smap.p, L.sbkg.p,
-                                        L.skey.p, dk.flags, dk.cnt, dk.list, kpi);
+                                        L.skey.p, dk.flags, dk.cnt, dk.list, L.rng.p, kpi);
     T.end();
     if (dk.tail_cnt || dk.pt_cnt) {  // the tiles that the correlation has to compute, per detector
       T.begin("k_tile_bound");
-      k_tile_bound<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, c->tb_lds, st>>>(
-          dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.flags, dk.tail_flags, dk.tail_cnt, dk.tail_list,
-          dk.pt_flags, dk.pt_cnt, dk.pt_list);
+      if (c->tb_ref)
+        k_tile_bound_ref<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, c->tb_lds, st>>>(
+            dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.flags, dk.tail_flags, dk.tail_cnt, dk.tail_list,
+            dk.pt_flags, dk.pt_cnt, dk.pt_list);
+      else
+        k_tile_bound<<<dim3((unsigned)nproc, (unsigned)(K.tbw_nband[0] + K.tbw_nband[1])), LM_TB_THREADS, c->tbw_lds,
+                       st>>>(dK, L.rng.p, c->ext_slot_bytes / LM_INGEST_VEC, s_proc0, nproc, c->tb_const.p, dk.flags,
+                             dk.tail_flags, dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list);
       T.end();
     }
   }

@@ -1,8 +1,9 @@
 /*
  * lm_tail_bound.h — an upper bound on a detector's scores over one 40 x 4
  * output tile, from per-row pixel ranges (plain C++: the host runtime, the
- * k_tile_bound kernel, tests/cpp/tail_bound_check.cpp and
- * tests/cpp/point_bound_check.cpp share it).  Written for the tail
+ * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
+ * tests/cpp/point_bound_check.cpp and tests/cpp/tile_window_check.cpp share
+ * it).  Written for the tail
  * detectors (hence the name); it serves the point detectors too.
  *
  * The pipeline uses only the sign of a tail score (threshold(> 0), then
@@ -135,6 +136,66 @@ LM_TB_HD inline bool lm_tb_tile_skip(const uint8_t* rmax, const uint8_t* rmin, i
       a = x > a ? x : a;
       b = n < b ? n : b;
     }
+    U += P[i] * (double)a - N[i] * (double)b;
+  }
+  return U < 0.0;
+}
+
+// The same predicate from window ranges, which hold the vertical part of
+// lm_tb_tile_skip's reduction once instead of once per tile and weight row:
+// the LM_TB_H output rows of a tile read, at weight row i, window rows
+// 4 ty + i .. 4 ty + i + 3, and that range is the same for every (ty, i) with
+// the same 4 ty + i.  A window table for oh output rows (a whole detector, or
+// a band of its tile rows whose first window row is row 0) has
+//   rows 0 .. lm_tb_win_full(oh, kh) - 1: the range over rows r .. r + 3, for
+//     the oh / 4 tile rows of four output rows;
+//   then, when oh % 4 != 0, kh rows for the last tile row: row i holds the
+//     range over its oh % 4 rows 4 (oh / 4) + i ...
+// ftx tile columns per row, as in the row ranges.
+LM_TB_HD inline int lm_tb_win_full(int oh, int kh) {
+  const int nf = oh / LM_TB_H;
+  return nf > 0 ? LM_TB_H * (nf - 1) + kh : 0;
+}
+LM_TB_HD inline int lm_tb_win_rows(int oh, int kh) {
+  return lm_tb_win_full(oh, kh) + (oh % LM_TB_H != 0 ? kh : 0);
+}
+// Row w of the window table: its first row-range row *r0 and row count *nr.
+LM_TB_HD inline void lm_tb_win_src(int oh, int kh, int w, int* r0, int* nr) {
+  const int full = lm_tb_win_full(oh, kh);
+  if (w < full) {
+    *r0 = w;
+    *nr = LM_TB_H;
+  } else {
+    *r0 = oh / LM_TB_H * LM_TB_H + (w - full);
+    *nr = oh % LM_TB_H;
+  }
+}
+// The table's first row of tile row ty (weight row i reads that row + i).
+LM_TB_HD inline int lm_tb_win_row0(int oh, int kh, int ty) {
+  return ty < oh / LM_TB_H ? LM_TB_H * ty : lm_tb_win_full(oh, kh);
+}
+// Entry (w, tx) of the window table from the row ranges.
+LM_TB_HD inline void lm_tb_window(const uint8_t* rmax, const uint8_t* rmin, int ftx, int oh, int kh, int w, int tx,
+                                  uint8_t* mx, uint8_t* mn) {
+  int r0, nr;
+  lm_tb_win_src(oh, kh, w, &r0, &nr);
+  unsigned a = 0u, b = 255u;
+  for (int r = 0; r < nr; ++r) {
+    const unsigned x = rmax[(r0 + r) * ftx + tx], n = rmin[(r0 + r) * ftx + tx];
+    a = x > a ? x : a;
+    b = n < b ? n : b;
+  }
+  *mx = (uint8_t)a;
+  *mn = (uint8_t)b;
+}
+// lm_tb_tile_skip from the window table: the tile whose first table row is
+// row0 (lm_tb_win_row0), column tx.  The sum runs over i in the same order
+// and in double, so the result is lm_tb_tile_skip's.
+LM_TB_HD inline bool lm_tb_tile_skip_win(const uint8_t* wmax, const uint8_t* wmin, int ftx, int kh, int row0, int tx,
+                                         const double* P, const double* N, double bias) {
+  double U = bias;
+  for (int i = 0; i < kh; ++i) {
+    const unsigned a = wmax[(row0 + i) * ftx + tx], b = wmin[(row0 + i) * ftx + tx];
     U += P[i] * (double)a - N[i] * (double)b;
   }
   return U < 0.0;
