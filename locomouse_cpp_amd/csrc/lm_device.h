@@ -149,6 +149,12 @@ struct LmConst {
   int32_t tbw_br[2], tbw_nband[2], tbw_blo[2], tbw_nbk[2], tbw_rows[2], tbw_v[2], tbw_work[2], tbw_lds[2];
   int32_t tbw_use[LM_NDET], tbw_pn[LM_NDET], tbw_win[LM_NDET], tbw_wsz[LM_NDET], tbw_ent[LM_NDET];
   uint32_t tbw_inv[LM_NDET];
+  // the refinement per output block and tap group (lm_tail_bound.h) of the
+  // tiles the tile bound fails: tbr_on[d]: detector d's tiles are refined
+  // (tb_skip[d] and LM_TILE_REFINE), in k_tile_bound when tbw_use[d] as well;
+  // its tbr_ng[d] tap groups per row; the group constants (lm_tbr_prepare's
+  // layout) at tbr_off[d] of the bound constants
+  int32_t tbr_on[LM_NDET], tbr_ng[LM_NDET], tbr_off[LM_NDET];
   // the point detectors' output region per view: output (y, x) has its
   // I_*_MOUSE pixel at ext (fl_my + y, fl_mx + x); fl_oh x fl_ow outputs
   int32_t fl_my[2], fl_mx[2], fl_oh[2], fl_ow[2];

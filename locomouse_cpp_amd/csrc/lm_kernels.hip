@@ -677,6 +677,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
 // ranges beyond the LDS) lists every tile (a point detector: every bright
 // tile).  tt_cnt / pt_cnt null: the tail / point detectors are not handled
 // here (LM_CORR_TAILSKIP=0 / LM_CORR_POINTSKIP=0).
+// A tile the tile bound fails is tried once more per 8-column output block and
+// group of 8 taps (LmConst::tbr_on, lm_tail_bound.h: lm_tbr_*), from the same
+// block ranges, and left out when every block of it is proven
+// (LM_TILE_REFINE=0: the tile bound alone).
 //
 // k_tile_bound_ref is the first form of the pre-pass (LM_TILE_BOUND_REF=1):
 // it reads the crops themselves and reduces a whole view per workgroup.  It is
@@ -796,6 +800,9 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
       mbr += br && keep ? 1 : 0;
       if (keep && use[k])
         keep = !lm_tb_tile_skip(rmax, rmin, ftx, D.oh, D.kh, i / ftx, i % ftx, P, P + D.kh, K.tb_bias[d]);
+      if (keep && use[k] && K.tbr_on[d] != 0)  // the refinement, block by block at the final height (no shortcut)
+        keep = !lm_tbr_tile_skip(bmax, bmin, nbw, D.in_y, D.in_x, D.oh, D.ow, D.kh, D.kw, i / ftx, i % ftx,
+                                 tbc + K.tbr_off[d], K.tb_bias[d], LM_TB_RH, false);
       fl[i] = keep ? 1 : 0;
       mine += keep ? 1 : 0;
     }
@@ -850,6 +857,8 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
 //   4. lm_tb_tile_skip_win per listed tile: kh pairs of bytes, the work list
 //      handed out densely.  Kept tiles take their place in the band's entries
 //      by a ballot and one LDS atomic per wave.
+//   4b. The refinement of the kept tiles, one pass per detector over (tile,
+//      output block) pairs (see there); the entries of proven tiles drop out.
 //   5. One global atomic per (workgroup, detector) on the slot group's segment
 //      counter (the segment index comes from the slot and the batch's slot
 //      count nslot, so all bands of a slot append to one segment), then the
@@ -879,7 +888,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list) {
   const LmConst& K = *Kp;
   extern __shared__ __attribute__((aligned(16))) uint8_t tbw_lds[];
-  __shared__ int s_n[3], s_b[3], s_base[3], s_nw;
+  __shared__ int s_n[3], s_b[3], s_m[3], s_base[3], s_nw;
   const int v = (int)blockIdx.y < K.tbw_nband[0] ? 0 : 1;
   const int band = (int)blockIdx.y - (v ? K.tbw_nband[0] : 0);
   const int slot = s0 + (int)blockIdx.x;
@@ -887,13 +896,14 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   if (tid < 3) {
     s_n[tid] = 0;
     s_b[tid] = 0;
+    s_m[tid] = 0;
   }
   if (tid == 0) s_nw = 0;
   // the view's detectors (paw, snout, tail: ids 3 v + k) in this band: on =
   // its tiles are listed here, use = with the bound; t0, nt: its first tile
   // row and tile count, ohb: its output rows; y_lo .. y_hi: the ext rows the
   // windows of the detectors with a bound span
-  bool on[3], use[3], tail[3];
+  bool on[3], use[3], refine[3], tail[3];
   int t0[3], nt[3], ohb[3], ftx[3], tbase[3];
   uint8_t* fl[3];
   int y_lo = K.ext_h[v], y_hi = 0;
@@ -912,6 +922,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     fl[k] = tail[k] ? tail_flags + (int64_t)slot * K.tt_slot + K.tt_off[v]
                     : pt_flags + (D.list & 1) * K.pt_plane + (int64_t)slot * K.fl_slot + K.fl_off[v];
     use[k] = use[k] && nt[k] > 0;
+    refine[k] = use[k] && K.tbr_on[d] != 0;
     if (use[k]) {  // (the host accepts a bound only when the window lies inside the ext crop)
       y_lo = min(y_lo, D.in_y + LM_FH * t0[k]);
       y_hi = max(y_hi, D.in_y + LM_FH * t0[k] + ohb[k] + D.kh - 1);
@@ -1059,7 +1070,8 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       keep = !lm_tb_tile_skip_win(wmax, wmax + TBW_SEL(wsz3), fx, kh, lm_tb_win_row0(TBW_SEL(ohb), kh, ty), tx, pn,
                                   pn + kh, TBW_SEL(bias3));
     }
-    if (act) TBW_SEL(fl)[tb + j] = keep ? 1 : 0;
+    // (a tile that goes on to the refinement gets its flag there)
+    if (act && !(keep && TBW_SEL(refine))) TBW_SEL(fl)[tb + j] = keep ? 1 : 0;
 #undef TBW_SEL
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {
@@ -1067,6 +1079,93 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       const int pos = wave_append(mine, &s_n[kk]);
       if (mine) reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_ent[3 * v + kk])[pos] = ((uint32_t)slot << 16) | (uint32_t)(tb + j);
     }
+  }
+  __syncthreads();
+  // 4b. the refinement of the tiles the tile bound failed, which now stand in
+  // the band's entries: one pass per detector, so that kh, the group count and
+  // the constants (scalar loads of tbc, a 64-byte chunk of four groups at a
+  // time) are uniform; one (tile, output block) per thread.  A block is tried
+  // over the tile's four rows first (V), then row by row (B) at LM_TB_RH 1 (or
+  // over the rows of a short last tile row); a tile with a block that stays
+  // unproven is marked and keeps its entry, the others get flag 0 and the
+  // entries close up.
+  uint32_t* mark = work;  // (the work list is done with)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!refine[k]) continue;
+    const int n = __builtin_amdgcn_readfirstlane(s_n[k]);
+    if (n == 0) continue;
+    const int d = 3 * v + k;
+    const LmDet& D = K.det[d];
+    uint32_t* ent = reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_ent[d]);
+    for (int t = tid; t < n; t += T) mark[t] = 0u;
+    __syncthreads();
+    const int kh = D.kh, ng = K.tbr_ng[d];
+    const double* __restrict__ C = tbc + K.tbr_off[d];
+    const double bias = K.tb_bias[d];
+    const int yb = D.in_y + LM_FH * t0[k] - y_lo;  // the band's window row 0 among the loaded rows
+    const int bl0 = lm_tbr_block0(D.in_x, 0) - K.tbw_blo[v];
+    const int bendl = lm_tbr_block_end(D.in_x, D.ow, D.kw, K.ext_w[v] / LM_TB_BLK) - K.tbw_blo[v];
+    const int nbx = (D.ow + LM_TB_BLK - 1) / LM_TB_BLK;
+    const uint32_t rcx = lm_rcp(LM_TB_NBX), rct = K.tbw_inv[d];
+    for (int e0 = 0; e0 < n * LM_TB_NBX; e0 += T) {
+      const int e = e0 + tid;
+      if (e >= n * LM_TB_NBX) continue;
+      const int t = lm_div(e, rcx);
+      const int tile = (int)(ent[t] & 0xFFFFu);
+      const int ty = lm_div(tile, rct), tx = tile - ty * ftx[k];
+      const int xb = tx * LM_TB_NBX + (e - t * LM_TB_NBX);
+      if (xb >= nbx) continue;  // (a last tile column of fewer blocks)
+      const int tyb = ty - t0[k];
+      const int nr = min(LM_TB_H, ohb[k] - LM_TB_H * tyb);
+      const int row0 = yb + LM_TB_H * tyb, ba0 = bl0 + xb;
+      // the tile's four rows at once from their windows V; rows rs .. rs + nn - 1 from the block ranges B
+      auto level_v = [&]() {
+        return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
+          const int ba = ba0 + g, bb = min(ba + 1, bendl - 1);
+          const uint16_t* row = V16 + (row0 + i) * nbk;
+          const unsigned qa = row[ba], qb = row[bb];
+          M = max(qa & 0xFFu, qb & 0xFFu);
+          m = min(qa >> 8, qb >> 8);
+        });
+      };
+      auto level_b = [&](int rs, int nn) {
+        return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
+          const int ba = ba0 + g, bb = min(ba + 1, bendl - 1);
+          const uint16_t* row = B16 + (row0 + rs + i) * nbk;
+          M = 0u;
+          m = 255u;
+          for (int r = 0; r < nn; ++r, row += nbk) {
+            const unsigned qa = row[ba], qb = row[bb];
+            M = max(M, max(qa & 0xFFu, qb & 0xFFu));
+            m = min(m, min(qa >> 8, qb >> 8));
+          }
+        });
+      };
+      bool proven = nr == LM_TB_H && level_v();
+      if (!proven && !(LM_TB_RH == LM_TB_H && nr == LM_TB_H)) {
+        if (LM_TB_RH == LM_TB_H) {
+          proven = level_b(0, nr);
+        } else {
+          proven = true;
+          for (int r = 0; r < nr && proven; ++r) proven = level_b(r, 1);
+        }
+      }
+      if (!proven) mark[t] = 1u;
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < n; c0 += T) {  // (a chunk's entries are read before any of them is overwritten)
+      const int t = c0 + tid;
+      const bool act = t < n;
+      const uint32_t e = act ? ent[t] : 0u;
+      const bool kp = act && mark[t] != 0u;
+      if (act) fl[k][e & 0xFFFFu] = kp ? 1 : 0;
+      __syncthreads();
+      const int pos = wave_append(kp, &s_m[k]);
+      if (kp) ent[pos] = e;
+    }
+    __syncthreads();
+    if (tid == 0) s_n[k] = s_m[k];
   }
   __syncthreads();
   // 5. this workgroup's list segments and their counters, as in k_ingest

@@ -227,7 +227,10 @@ struct lm_ctx {
   // LM_TILE_BOUND_REF=1: the pre-pass is k_tile_bound_ref (it reads the crops;
   // k_ingest then writes no block ranges)
   bool tb_ref = false;
-  DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off)
+  // LM_TILE_REFINE=0: the tile bound alone decides (no refinement per output
+  // block and tap group), in both kernels
+  bool tb_refine = true;
+  DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off), then its P[i][g], N[i][g] (tbr_off)
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
   DevBuf<uint8_t> handoff;     // two frames: the last frame of submitted batch k in slot k & 1
@@ -711,6 +714,7 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   if (const char* v = getenv("LM_CORR_POINTSKIP")) c->pointskip_on = atoi(v) != 0;
   if (su->corr_precision == LM_CORR_F16) c->tailskip_on = c->pointskip_on = false;  // the bound is for the fp32 chain
   if (!c->dark_on) c->pointskip_on = false;  // it starts from k_ingest's bright flags
+  if (const char* v = getenv("LM_TILE_REFINE")) c->tb_refine = atoi(v) != 0;
   {
     int o = 0, mt = 0;
     for (int t = 0; t < 2; ++t) {
@@ -751,6 +755,15 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
         if (K.tb_skip[d]) {
           lds += need;
           any = true;
+        }
+        // the refinement's constants per tap group (off wherever the skip is)
+        K.tbr_on[d] = K.tb_skip[d] && c->tb_refine ? 1 : 0;
+        K.tbr_ng[d] = K.tbr_on[d] ? lm_tbr_groups(D.in_x, D.kw) : 0;
+        tbc.resize((tbc.size() + 7) / 8 * 8);  // (a chunk of group constants is 64 bytes, kept aligned)
+        K.tbr_off[d] = (int32_t)tbc.size();
+        if (K.tbr_on[d]) {
+          tbc.resize(tbc.size() + (size_t)lm_tbr_const_size(D.kh, K.tbr_ng[d]));
+          lm_tbr_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.in_x, tbc.data() + K.tbr_off[d]);
         }
       }
       K.tb_lds[v] = any ? (int32_t)lds : 0;

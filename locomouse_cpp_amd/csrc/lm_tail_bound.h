@@ -2,8 +2,9 @@
  * lm_tail_bound.h — an upper bound on a detector's scores over one 40 x 4
  * output tile, from per-row pixel ranges (plain C++: the host runtime, the
  * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
- * tests/cpp/point_bound_check.cpp and tests/cpp/tile_window_check.cpp share
- * it).  Written for the tail
+ * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp and
+ * tests/cpp/tile_refine_check.cpp share it), and its refinement per 8-column
+ * output block and tap group (below, lm_tbr_*).  Written for the tail
  * detectors (hence the name); it serves the point detectors too.
  *
  * The pipeline uses only the sign of a tail score (threshold(> 0), then
@@ -199,6 +200,155 @@ LM_TB_HD inline bool lm_tb_tile_skip_win(const uint8_t* wmax, const uint8_t* wmi
     U += P[i] * (double)a - N[i] * (double)b;
   }
   return U < 0.0;
+}
+
+// ------------------------------------------------------------------------
+// The refinement: the same bound per 8-column output block and group of 8
+// taps, for the tiles the tile bound fails.  The tile bound takes one pixel
+// range per weight row over a tile's whole 40 + kw - 1 columns and four rows,
+// so a tile within a detector's reach of an edge sees the full step in every
+// row.  Here the outputs are cut into blocks of LM_TB_BLK columns (x0 a
+// multiple of 8; 40 is one) and LM_TB_RH rows, and the taps of a weight row
+// into groups that end where in_x + j is a multiple of 8 (in_x: the view
+// column of the window's column 0, the view being the ext crop whose aligned
+// blocks of 8 columns the ranges are taken over): tap j is in group
+// (in_x % 8 + j) / 8.  The 8 outputs of a block then read, at the taps of
+// group g, view columns 8 (in_x / 8 + g + x0 / 8) .. + 15: two adjacent
+// aligned blocks.  With P[i][g] / N[i][g] the sums of the positive and of the
+// negated negative weights of row i's group g (rounded as P_i, N_i are) and
+// M / m the largest / smallest pixel of those two blocks over the view rows
+// in_y + y + i .. + nr - 1 (the second block clipped to the blocks the
+// detector's window touches: beyond them no output inside ow reads),
+//     U = bias + sum_i sum_g (P[i][g] M - N[i][g] m)
+// bounds every score of the block from above, by the argument at the top term
+// by term, and bias is the same: the chain's rounding does not depend on how
+// the bound is split, and kh (kw + 7) / 8 + kh terms in double stay far inside
+// its 1e-6 relative share.  A tile is skipped iff the tile bound proves it or
+// every block of it is proven.
+// A block proven over four rows is proven in each row: a row's ranges lie
+// inside the four rows', so each of its terms is <= the matching term (the
+// roundings of the products and of the difference are monotone) and the sums
+// run in the same order.  With LM_TB_RH 1 the four-row level is therefore a
+// shortcut that never changes a flag (`shortcut`; both forms are kept so that
+// a test can compare them).  A last tile row of fewer than four output rows
+// uses its own row count.
+#ifndef LM_TB_RH
+#define LM_TB_RH 4  // rows of an output block at the final level: 1 or 4
+#endif
+#define LM_TB_NBX (LM_TB_W / LM_TB_BLK)  // output blocks per tile row
+static_assert(LM_TB_RH == 1 || LM_TB_RH == LM_TB_H, "block height: a row or a tile");
+static_assert(LM_TB_W % LM_TB_BLK == 0, "tiles start on a block boundary");
+
+// Tap groups of a detector row (in_x >= 0) and the taps [*j0, *j1) of group g.
+LM_TB_HD inline int lm_tbr_groups(int in_x, int kw) { return (in_x % LM_TB_BLK + kw - 1) / LM_TB_BLK + 1; }
+LM_TB_HD inline void lm_tbr_taps(int in_x, int kw, int g, int* j0, int* j1) {
+  const int a = in_x % LM_TB_BLK;
+  *j0 = LM_TB_BLK * g - a > 0 ? LM_TB_BLK * g - a : 0;
+  *j1 = LM_TB_BLK * (g + 1) - a < kw ? LM_TB_BLK * (g + 1) - a : kw;
+}
+// The group constants of a detector: per weight row i and chunk c of
+// LM_TBR_GC groups, LM_TBR_GC values of P (groups GC c ..) and then of N,
+// lm_tb_prepare's sums per group; groups past the last hold 0.  (One chunk is
+// 64 bytes: a kernel whose detector is uniform fetches it with one scalar
+// load.)  lm_tbr_const_size() doubles in all.
+#define LM_TBR_GC 4
+LM_TB_HD inline int lm_tbr_chunks(int ng) { return (ng + LM_TBR_GC - 1) / LM_TBR_GC; }
+LM_TB_HD inline int lm_tbr_const_size(int kh, int ng) { return kh * lm_tbr_chunks(ng) * 2 * LM_TBR_GC; }
+LM_TB_HD inline void lm_tbr_prepare(const float* w, int kh, int kw, int wstride, int in_x, double* C) {
+  const int ng = lm_tbr_groups(in_x, kw), nc = lm_tbr_chunks(ng);
+  for (int i = 0; i < kh; ++i)
+    for (int g = 0; g < nc * LM_TBR_GC; ++g) {
+      int j0 = 0, j1 = 0;
+      if (g < ng) lm_tbr_taps(in_x, kw, g, &j0, &j1);
+      double p = 0.0, n = 0.0;
+      for (int j = j0; j < j1; ++j) {
+        const double v = (double)w[i * wstride + j];
+        if (v > 0.0) p += v;
+        else if (v < 0.0) n -= v;
+      }
+      double* q = C + ((i * nc + g / LM_TBR_GC) * 2) * LM_TBR_GC + g % LM_TBR_GC;
+      q[0] = p * (1.0 + 1e-12);          // rounded up
+      q[LM_TBR_GC] = n * (1.0 - 1e-12);  // rounded down (it is subtracted)
+    }
+}
+// The one definition of a block's sum: rng(i, g, M, m) yields the largest and
+// smallest byte of weight row i's group g (unsigned references).  Every user
+// (the host, k_tile_bound_ref, k_tile_bound) goes through it, so equal ranges
+// give the same bit.
+template <class F>
+LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double bias, F&& rng) {
+  static_assert(LM_TBR_GC == 4, "a chunk is read as four P and four N");
+  const int nc = lm_tbr_chunks(ng);
+  double U = bias;
+  for (int i = 0; i < kh; ++i)
+    for (int c = 0; c < nc; ++c) {
+      const double* q = C + (i * nc + c) * 2 * LM_TBR_GC;
+      const double p0 = q[0], p1 = q[1], p2 = q[2], p3 = q[3], n0 = q[4], n1 = q[5], n2 = q[6], n3 = q[7];
+      const int g = c * LM_TBR_GC;
+      unsigned M, m;
+      rng(i, g, M, m);
+      U += p0 * (double)M - n0 * (double)m;
+      if (g + 1 < ng) {
+        rng(i, g + 1, M, m);
+        U += p1 * (double)M - n1 * (double)m;
+      }
+      if (g + 2 < ng) {
+        rng(i, g + 2, M, m);
+        U += p2 * (double)M - n2 * (double)m;
+      }
+      if (g + 3 < ng) {
+        rng(i, g + 3, M, m);
+        U += p3 * (double)M - n3 * (double)m;
+      }
+    }
+  return U < 0.0;
+}
+// First block (of the view's) that output block xb reads at group 0, and the
+// end of the blocks the window touches (nbw: blocks per view row).
+LM_TB_HD inline int lm_tbr_block0(int in_x, int xb) { return in_x / LM_TB_BLK + xb; }
+LM_TB_HD inline int lm_tbr_block_end(int in_x, int ow, int kw, int nbw) {
+  const int e = (in_x + ow + kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK;
+  return e < nbw ? e : nbw;
+}
+// The output block of rows [y, y + nr) and columns [8 xb, 8 xb + 8) from the
+// view's block ranges bmax / bmin ([view row][nbw blocks]): true = proven.
+LM_TB_HD inline bool lm_tbr_block_skip(const uint8_t* bmax, const uint8_t* bmin, int nbw, int in_y, int in_x, int ow,
+                                       int kh, int kw, int y, int nr, int xb, const double* C, double bias) {
+  const int b0 = lm_tbr_block0(in_x, xb), bend = lm_tbr_block_end(in_x, ow, kw, nbw);
+  return lm_tbr_sum_negative(kh, lm_tbr_groups(in_x, kw), C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
+    const int ba = b0 + g, bb = ba + 1 < bend ? ba + 1 : bend - 1;
+    M = 0u;
+    m = 255u;
+    for (int r = 0; r < nr; ++r) {
+      const int row = (in_y + y + i + r) * nbw;
+      const unsigned xa = bmax[row + ba], xb2 = bmax[row + bb], na = bmin[row + ba], nb = bmin[row + bb];
+      M = xa > M ? xa : M;
+      M = xb2 > M ? xb2 : M;
+      m = na < m ? na : m;
+      m = nb < m ? nb : m;
+    }
+  });
+}
+// The tile rule's second half for tile (ty, tx): every block proven at block
+// height rh (1 or LM_TB_H).
+LM_TB_HD inline bool lm_tbr_tile_skip(const uint8_t* bmax, const uint8_t* bmin, int nbw, int in_y, int in_x, int oh,
+                                      int ow, int kh, int kw, int ty, int tx, const double* C, double bias, int rh,
+                                      bool shortcut) {
+  const int y0 = ty * LM_TB_H;
+  const int nr = (y0 + LM_TB_H < oh ? y0 + LM_TB_H : oh) - y0;
+  const int nbx = (ow + LM_TB_BLK - 1) / LM_TB_BLK;
+  for (int xb = tx * LM_TB_NBX; xb < (tx + 1) * LM_TB_NBX && xb < nbx; ++xb) {
+    if (rh != 1) {
+      if (!lm_tbr_block_skip(bmax, bmin, nbw, in_y, in_x, ow, kh, kw, y0, nr, xb, C, bias)) return false;
+      continue;
+    }
+    if (shortcut && nr == LM_TB_H &&
+        lm_tbr_block_skip(bmax, bmin, nbw, in_y, in_x, ow, kh, kw, y0, nr, xb, C, bias))
+      continue;
+    for (int r = 0; r < nr; ++r)
+      if (!lm_tbr_block_skip(bmax, bmin, nbw, in_y, in_x, ow, kh, kw, y0 + r, 1, xb, C, bias)) return false;
+  }
+  return true;
 }
 
 #endif  // LM_TAIL_BOUND_H
