@@ -175,6 +175,8 @@ BB_FRAME_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y_bottom", "y_side", "widt
 LM_JPEG_OK, LM_JPEG_NEEDS_HOST, LM_JPEG_REJECTED = 0, 1, 2
 LM_JPEG_SUBSEQ_MIN, LM_JPEG_SUBSEQ_DEFAULT, LM_JPEG_CHUNK = 4, 64, 128
 LM_BKG_MAX_SAMPLES = 65535  # include/locomouse_bkg.h: frames one lm_bkg_ctx accumulates
+# include/locomouse_train.h
+LM_TRAIN_MAX_SIDE, LM_TRAIN_MAX_SAMPLES = 64, 1 << 22
 # include/locomouse_encode.h
 LM_ENC_GRAY8, LM_ENC_RGB24 = 0, 1
 LM_ENC_BLOCK_WORDS, LM_ENC_MAX_HEADER, LM_ENC_MAX_BLOCKS, LM_ENC_MAX_BATCH, LM_ENC_MAX_RADIUS = 52, 640, 1 << 20, 4096, 64
@@ -189,6 +191,22 @@ class lm_enc_result(C.Structure):
         ("data", C.c_void_p),
         ("offset", C.POINTER(C.c_uint32)),
         ("size", C.POINTER(C.c_uint32)),
+    ]
+
+
+class lm_train_point(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("label", C.c_int32)]
+
+
+class lm_train_stats(C.Structure):
+    _fields_ = [
+        ("objective", C.c_double),
+        ("grad_norm", C.c_double),
+        ("grad_norm0", C.c_double),
+        ("outer_iters", C.c_int32),
+        ("cg_iters", C.c_int32),
+        ("converged", C.c_int32),
+        ("n_active", C.c_int32),
     ]
 
 

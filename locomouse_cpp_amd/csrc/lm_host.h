@@ -175,4 +175,16 @@ lm_status guarded(F&& f) {
 hipError_t launch_minmax_lut(const uint8_t* const* frame_ptr, const uint8_t* bkg, int npix, int s0, int n,
                              unsigned* mm, const uint8_t* adj, int use_adj, uint8_t* luts, hipStream_t st);
 
+// What lm_train.hip's gather takes from a detection context (lm_runtime.hip):
+// its device constants and frame-invariant images, all on `device`.
+struct LmTrainView {
+  int device, npix;        // npix: bytes of a video frame
+  int n_rows, n_cols;      // corrected image
+  int use_adj, gray_lut_on;
+  const void* dK;          // LmConst in device memory
+  const uint8_t *bkg, *adj;
+  const int32_t* cal;
+};
+void lm_ctx_train_view(const lm_ctx* c, LmTrainView* v);
+
 #endif  // LM_HOST_H

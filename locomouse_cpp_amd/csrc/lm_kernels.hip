@@ -38,19 +38,7 @@
 
 // ------------------------------------------------------------------ helpers
 
-template <class FP>
-DEV uint8_t ipad_pixel(FP __restrict__ F, const uint8_t* __restrict__ bkg,
-                       const int32_t* __restrict__ cal, const uint8_t* lut, const LmConst& K, int R, int C) {
-  // I_PAD(R, C): zero outside I_UNPAD (:684-689); inside, the corrected,
-  // normalised, optionally flipped frame.
-  const int r = R - K.pad_pre_rows;
-  int c = C - K.pad_pre_cols;
-  if (r < 0 || r >= K.n_rows || c < 0 || c >= K.n_cols) return 0;
-  if (K.flip) c = K.n_cols - 1 - c;
-  const int idx = cal[r * K.n_cols + c];
-  const int f = F[idx], b = bkg[idx];
-  return lut[f > b ? f - b : 0];
-}
+// (ipad_pixel: lm_dev_common.h, shared with lm_train.hip's gather)
 
 // --------------------------------------------------------------- k_minmax
 // normalize(F, F, 0, 255, NORM_MINMAX, CV_8UC1) after subtract(F, BKG, F)

@@ -2255,3 +2255,17 @@ hipError_t launch_minmax_lut(const uint8_t* const* frame_ptr, const uint8_t* bkg
   k_lut<<<(n - s0 + 3) / 4, 256, 0, st>>>(mm, s0, n, adj, use_adj, luts);
   return hipGetLastError();
 }
+
+// the detection context as lm_train.hip's gather reads it (its own translation unit)
+void lm_ctx_train_view(const lm_ctx* c, LmTrainView* v) {
+  v->device = c->device;
+  v->npix = c->npix;
+  v->n_rows = c->K.n_rows;
+  v->n_cols = c->K.n_cols;
+  v->use_adj = c->setup.method != 0;
+  v->gray_lut_on = c->K.gray_lut_on;
+  v->dK = c->dK.p;
+  v->bkg = c->bkg.p;
+  v->adj = c->adj.p;
+  v->cal = c->cal.p;
+}

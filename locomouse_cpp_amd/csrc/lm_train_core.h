@@ -1,0 +1,128 @@
+// lm_train_core.h — the detector training's arithmetic (include/locomouse_train.h),
+// compiled for host and device: a sample's part of the objective, of its
+// gradient and of the line search, and the host statement of the whole (CPU
+// tests; the kernels of lm_train.hip compute the same sums in their own fixed
+// order).  Doubles only.
+//
+//   F(w, b) = 1/2 (|w|^2 + b^2) + sum_i C_{y_i} max(0, 1 - y_i z_i)^2,   z_i = w . x_i + b,  x_i = p_i / 255
+//
+// The matrix products run over the u8 patches p_i as they are stored (the
+// conversion u8 -> double is exact) and are divided by 255 once per sum:
+// z_i = (w . p_i) / 255 + b,  (X^T t)_j = (sum_i t_i p_ij) / 255.
+//
+// A sample matrix is N rows of D = kh * kw bytes, lmt_pitch(D) bytes apart,
+// the bytes past D zero.
+#ifndef LM_TRAIN_CORE_H
+#define LM_TRAIN_CORE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LMT_HD __host__ __device__ inline
+#else
+#define LMT_HD inline
+#endif
+
+#define LMT_LS_STEPS 24       // line search: lambda = 2^-k, k = 0 .. LMT_LS_STEPS - 1
+#define LMT_ARMIJO 1e-4       // F(w + lambda d) - F(w) <= LMT_ARMIJO lambda g . d
+#define LMT_CG_TOL 1e-3       // CG stops at |r| <= LMT_CG_TOL |g|
+#define LMT_XT_BLOCK 1024     // samples per block of the X^T u pass (lm_train.hip's k_train_xt)
+
+LMT_HD int lmt_pitch(int D) { return (D + 15) / 16 * 16; }
+
+// Sample i at margin z: its cost a = C_{y} when it is active (y z < 1), else 0;
+// *t = a (z - y), its coefficient in grad F = (w, b) + 2 X~^T t (y^2 = 1);
+// *loss = a (1 - y z)^2.
+LMT_HD double lmt_coef(int y, double z, double c_pos, double c_neg, double* t, double* loss) {
+  const double yd = (double)y;
+  const double m = 1.0 - yd * z;
+  const double a = m > 0.0 ? (y > 0 ? c_pos : c_neg) : 0.0;
+  *t = a * (z - yd);
+  *loss = a * (m * m);
+  return a;
+}
+
+// The change of sample i's loss when its margin goes from z to z + lambda xd.
+LMT_HD double lmt_ls_delta(int y, double z, double xd, double lambda, double c_pos, double c_neg) {
+  const double yd = (double)y, c = y > 0 ? c_pos : c_neg;
+  double m0 = 1.0 - yd * z, m1 = 1.0 - yd * (z + lambda * xd);
+  m0 = m0 > 0.0 ? m0 : 0.0;
+  m1 = m1 > 0.0 ? m1 : 0.0;
+  return c * ((m1 - m0) * (m1 + m0));
+}
+
+// ---- the host statement.  Vectors are D + 1 doubles: w, then b.
+
+// z_i = (w . p_i) / 255 + b
+inline void lmt_host_margins(const uint8_t* X, int64_t pitch, int64_t N, int D, const double* wb, double* z) {
+  for (int64_t i = 0; i < N; ++i) {
+    const uint8_t* p = X + i * pitch;
+    double s = 0.0;
+    for (int j = 0; j < D; ++j) s += wb[j] * (double)p[j];
+    z[i] = s / 255.0 + wb[D];
+  }
+}
+
+// out = X~^T t: out_j = (sum_i t_i p_ij) / 255, out_D = sum_i t_i
+inline void lmt_host_xt(const uint8_t* X, int64_t pitch, int64_t N, int D, const double* t, double* out) {
+  for (int j = 0; j <= D; ++j) out[j] = 0.0;
+  for (int64_t i = 0; i < N; ++i) {
+    const uint8_t* p = X + i * pitch;
+    for (int j = 0; j < D; ++j) out[j] += t[i] * (double)p[j];
+    out[D] += t[i];
+  }
+  for (int j = 0; j < D; ++j) out[j] /= 255.0;
+}
+
+// F and grad F at wb; a (N doubles) gets the active costs.  Returns the number of active samples.
+inline int64_t lmt_host_objective(const uint8_t* X, int64_t pitch, const int8_t* y, int64_t N, int D, double c_pos,
+                                  double c_neg, const double* wb, double* z, double* a, double* t, double* F,
+                                  double* grad) {
+  lmt_host_margins(X, pitch, N, D, wb, z);
+  double f = 0.0;
+  int64_t n_active = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    double loss;
+    a[i] = lmt_coef(y[i], z[i], c_pos, c_neg, &t[i], &loss);
+    f += loss;
+    n_active += a[i] != 0.0;
+  }
+  double reg = 0.0;
+  for (int j = 0; j <= D; ++j) reg += wb[j] * wb[j];
+  *F = 0.5 * reg + f;
+  lmt_host_xt(X, pitch, N, D, t, grad);
+  for (int j = 0; j <= D; ++j) grad[j] = wb[j] + 2.0 * grad[j];
+  return n_active;
+}
+
+// out = (I + 2 X~_A^T C_A X~_A) v with the active costs a; u, au: N doubles of scratch
+inline void lmt_host_hessvec(const uint8_t* X, int64_t pitch, int64_t N, int D, const double* a, const double* v,
+                             double* u, double* out) {
+  lmt_host_margins(X, pitch, N, D, v, u);
+  for (int64_t i = 0; i < N; ++i) u[i] *= a[i];
+  lmt_host_xt(X, pitch, N, D, u, out);
+  for (int j = 0; j <= D; ++j) out[j] = v[j] + 2.0 * out[j];
+}
+
+// Armijo backtracking from the cached margins z and xd = X~ d: the first
+// lambda = 2^-k with F(wb + lambda d) - F(wb) <= LMT_ARMIJO lambda g.d, where
+// wd = wb . d, dd = d . d, gd = g . d.  Returns k, or -1 when none of the
+// LMT_LS_STEPS holds; *dF is the change of F at the step taken.
+inline int lmt_host_linesearch(const int8_t* y, const double* z, const double* xd, int64_t N, double c_pos, double c_neg,
+                               double wd, double dd, double gd, double* dF) {
+  double lambda = 1.0;
+  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
+    double s = 0.0;
+    for (int64_t i = 0; i < N; ++i) s += lmt_ls_delta(y[i], z[i], xd[i], lambda, c_pos, c_neg);
+    const double d = lambda * wd + 0.5 * lambda * lambda * dd + s;
+    if (d <= LMT_ARMIJO * lambda * gd) {
+      *dF = d;
+      return k;
+    }
+  }
+  *dF = 0.0;
+  return -1;
+}
+
+#endif  // LM_TRAIN_CORE_H

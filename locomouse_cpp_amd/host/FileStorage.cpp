@@ -486,4 +486,21 @@ void FsWriter::write_mat_i(const int* data, int rows, int cols) {
   name_expected_ = stack_.back().map;
 }
 
+void FsWriter::write_mat_d(const double* data, int rows, int cols) {
+  if (!isOpened()) return;
+  start(stack_.back().map ? elname_.c_str() : nullptr, true, false, "opencv-matrix");
+  elname_.clear();
+  name_expected_ = true;
+  *this << "rows" << rows << "cols" << cols << "dt" << "d" << "data" << "[:";
+  for (long long k = 0; k < (long long)rows * cols; ++k) {
+    if (data[k] == 0.0 && std::signbit(data[k]))
+      value("-0.");  // (fs_real drops the sign of zero)
+    else
+      *this << data[k];
+  }
+  *this << "]";
+  end();
+  name_expected_ = stack_.back().map;
+}
+
 }  // namespace locomouse

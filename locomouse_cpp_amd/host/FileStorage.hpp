@@ -72,6 +72,8 @@ class FsWriter {
   FsWriter& operator<<(double v);
   // An int32 matrix (rows x cols, row-major) as !!opencv-matrix with dt: i.
   void write_mat_i(const int* data, int rows, int cols);
+  // A double matrix with dt: d; "%.16e" reads back to the same double.
+  void write_mat_d(const double* data, int rows, int cols);
 
  private:
   struct Level {

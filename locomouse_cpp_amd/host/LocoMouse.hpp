@@ -156,6 +156,9 @@ class LocoMouse : protected FrameResults {
   const TrackResults& tracks() const { return TRACKS; }  // TRACK_INDEX_* and the exported matrices
   int current_frame() const { return CURRENT_FRAME; }
   lm_geometry geometry() const;
+  // The (first) device's detection context, once initializeFeatureLoop() has
+  // run (NULL before): what lm_train_gather cuts its patches through.
+  lm_ctx* context() const { return CTX; }
 
   // Processes the frames read so far (called by every accessor above).
   void sync();

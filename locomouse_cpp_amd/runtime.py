@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 
 from .abi import (BB_FRAME_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result, lm_enc_mark,
-                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_stats, result_to_numpy)
+                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_stats, lm_train_point,
+                  lm_train_stats, result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -40,7 +41,8 @@ CLI_PATH = os.path.join(PKG, "bin", "LocoMouse")
 
 
 # translation units of liblocomouse_hip.so
-HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip", "lm_jpeg_enc.hip")
+HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip", "lm_jpeg_enc.hip",
+             "lm_train.hip")
 
 # include/locomouse_jpeg.h (device MJPEG decode), same library
 JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
@@ -55,6 +57,12 @@ BKG_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseBackground")
 ENC_EXPORTED = ("lm_enc_slot_bytes", "lm_enc_create", "lm_enc_destroy", "lm_enc_encode_device", "lm_enc_encode",
                 "lm_enc_set_overlay", "lm_enc_render_encode_device", "lm_enc_render_encode", "lm_enc_render_device", "lm_enc_stream",
                 "lm_enc_last_stats")
+
+# include/locomouse_train.h (detector weights trained from labelled patches), same library
+TRAIN_EXPORTED = ("lm_train_create", "lm_train_destroy", "lm_train_add_patches", "lm_train_gather",
+                  "lm_train_gather_device", "lm_train_samples", "lm_train_reset", "lm_train_patches", "lm_train_solve",
+                  "lm_train_margins", "lm_train_stream")
+TRAIN_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTrain")
 
 
 def _up_to_date(obj, cmd):
@@ -112,7 +120,7 @@ def build_host(verbose=False):
     surface (locomouse_cpp_amd/host) linked against the C-ABI library."""
     srcs = [os.path.join(HOST_DIR, f)
             for f in ("LocoMouse.cpp", "Tracks.cpp", "match2nd.cpp", "FileStorage.cpp", "Media.cpp", "Jpeg.cpp", "Debug.cpp",
-                      "Background.cpp", "JpegEncode.cpp", "Preview.cpp")]
+                      "Background.cpp", "JpegEncode.cpp", "Preview.cpp", "Inputs.cpp", "Train.cpp")]
     flags = ["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
              "-I" + HOST_DIR]
     cmd = [*flags, "-fPIC", "-shared", "-o", HOST_LIB_PATH, *srcs, "-L" + PKG, "-llocomouse_hip", "-lz",
@@ -129,6 +137,12 @@ def build_host(verbose=False):
     subprocess.check_call(cmd)
     # LocoMouseBackground video.avi out.png [stride [permille]]: the background image the program above takes
     cmd = [*flags, "-o", BKG_CLI_PATH, os.path.join(HOST_DIR, "BackgroundCli.cpp"), "-L" + PKG, "-llocomouse_host",
+           "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # LocoMouseTrain: detector weights (a model.yml) trained from labelled frames (host/Train.hpp)
+    cmd = [*flags, "-o", TRAIN_CLI_PATH, os.path.join(HOST_DIR, "TrainCli.cpp"), "-L" + PKG, "-llocomouse_host",
            "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
     if verbose:
         print(" ".join(cmd))
@@ -225,6 +239,19 @@ def lib():
         L.lm_enc_stream.argtypes = [C.c_void_p]
         L.lm_enc_stream.restype = C.c_void_p
         L.lm_enc_last_stats.argtypes = [C.c_void_p, C.POINTER(lm_enc_stats)]
+        L.lm_train_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lm_train_destroy.argtypes = [C.c_void_p]
+        L.lm_train_add_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        for fn in (L.lm_train_gather, L.lm_train_gather_device):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32]
+        L.lm_train_samples.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.lm_train_reset.argtypes = [C.c_void_p]
+        L.lm_train_patches.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.lm_train_solve.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p,
+                                     C.POINTER(C.c_double), C.POINTER(lm_train_stats)]
+        L.lm_train_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        L.lm_train_stream.argtypes = [C.c_void_p]
+        L.lm_train_stream.restype = C.c_void_p
         _lib = L
     return _lib
 
@@ -609,6 +636,95 @@ class BackgroundEstimator:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lm_bkg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Trainer:
+    """One lm_train_ctx: kh x kw u8 patches with labels +1 / -1 on one HIP
+    device, and the L2-regularised squared-hinge SVM solved on them in fp64
+    (include/locomouse_train.h).  solve() returns the detector (W, rho) whose
+    score sum(W * patch) - rho is the SVM's margin, and the solver's stats."""
+
+    def __init__(self, kh, kw, max_samples, device=0):
+        self._h = C.c_void_p()
+        _check(lib().lm_train_create(device, kh, kw, max_samples, C.byref(self._h)))
+        self.kh, self.kw, self.max_samples, self.device = kh, kw, max_samples, device
+
+    def add_patches(self, patches, labels):
+        """patches [n, kh, kw] or [n, kh * kw] u8, labels [n] of +1 / -1."""
+        patches = np.ascontiguousarray(patches, dtype=np.uint8)
+        labels = np.ascontiguousarray(labels, dtype=np.int8)
+        n = labels.shape[0]
+        if patches.size != n * self.kh * self.kw:
+            raise ValueError(f"patches must hold {n} x {self.kh} x {self.kw} bytes, not {patches.shape}")
+        _check(lib().lm_train_add_patches(self._h, patches.ctypes.data, labels.ctypes.data, n))
+
+    @staticmethod
+    def _points(points):
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 4)  # (frame, x, y, label)
+        return pts, pts.ctypes.data if len(pts) else None
+
+    def gather(self, ctx, frames, points):
+        """One patch per point (frame, x, y, label), x and y in the corrected
+        image, cut from host frames [n, rows, cols] u8 as the detection
+        Context `ctx` reads them."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        pts, pp = self._points(points)
+        _check(lib().lm_train_gather(self._h, ctx._h, frames.ctypes.data, frames.shape[1] * frames.shape[2],
+                                     frames.shape[0], pp, len(pts)))
+
+    def gather_device(self, ctx, d_frames_ptr, pitch, n_frames, points):
+        """The same for frames in device memory (frame i at d_frames_ptr + i * pitch)."""
+        pts, pp = self._points(points)
+        _check(lib().lm_train_gather_device(self._h, ctx._h, C.c_void_p(d_frames_ptr), pitch, n_frames, pp, len(pts)))
+
+    def samples(self):
+        """(positives, negatives) stored."""
+        a, b = C.c_int32(), C.c_int32()
+        _check(lib().lm_train_samples(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def reset(self):
+        _check(lib().lm_train_reset(self._h))
+
+    def patches(self, first=0, n=None):
+        """(patches [n, kh, kw] u8, labels [n] int8) as they are stored."""
+        if n is None:
+            n = sum(self.samples()) - first
+        out = np.zeros((n, self.kh, self.kw), np.uint8)
+        lab = np.zeros(n, np.int8)
+        _check(lib().lm_train_patches(self._h, first, n, out.ctypes.data, lab.ctypes.data))
+        return out, lab
+
+    def solve(self, c_pos=10.0, c_neg=1.0, eps=1e-6, max_iter=100):
+        """(W [kh, kw] float64, rho, stats dict)."""
+        W = np.zeros((self.kh, self.kw), np.float64)
+        rho = C.c_double()
+        st = lm_train_stats()
+        _check(lib().lm_train_solve(self._h, c_pos, c_neg, eps, max_iter, W.ctypes.data, C.byref(rho), C.byref(st)))
+        return W, rho.value, {n: getattr(st, n) for n, _ in lm_train_stats._fields_}
+
+    def margins(self, W, rho):
+        """z_i = sum(W * patch_i) - rho of the stored samples."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.size != self.kh * self.kw:
+            raise ValueError(f"W must hold {self.kh} x {self.kw} doubles, not {W.shape}")
+        z = np.zeros(sum(self.samples()), np.float64)
+        _check(lib().lm_train_margins(self._h, W.ctypes.data, float(rho), z.ctypes.data))
+        return z
+
+    def stream(self):
+        return lib().lm_train_stream(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().lm_train_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
