@@ -22,7 +22,25 @@
  *
  * Every device buffer is sized from this worst case, so no frame can overflow
  * and there is no overflow path.  B is ceil(rows / 8) * ceil(cols / 8) for
- * grey and 6 * ceil(rows / 16) * ceil(cols / 16) for colour. */
+ * grey and 6 * ceil(rows / 16) * ceil(cols / 16) for colour.
+ *
+ * Restart intervals (lm_enc_create_restart).  With a restart interval of Ri
+ * MCUs (an MCU is one block for grey and six for colour) the scan has
+ * I = ceil(MCUs / Ri) intervals.  Every interval but the last ends in a 1-bit
+ * fill to a byte boundary, at most 7 bits, and an unstuffed 2-byte marker; the
+ * last ends in the frame's own fill, at most 7 bits as before.  The bound above
+ * spends 52 * 32 - 1660 = 4 spare bits per block on the frame's one fill, which
+ * an interval of one block outgrows: 1660 + 7 bits.  So the fills get words of
+ * their own, a byte each:
+ *
+ *   unstuffed bits  <= 1660 * B + 7 * I <= 32 * (52 * B + ceil(I / 4))
+ *   W               =  52 * B + ceil(I / 4) + 1 words (one spare, as above)
+ *   lm_enc_slot_bytes_restart = LM_ENC_MAX_HEADER + 2 * 4 * W + 2 * (I - 1) + 2
+ *
+ * that is at most 415 * B + 4 per interval of stream: a fill byte may be FF and
+ * is stuffed like any other (2 bytes), and the marker is 2.  The header with
+ * its DRI segment is 629 bytes.  Every device buffer of such a context is sized
+ * from this bound, so again no frame can overflow. */
 #ifndef LOCOMOUSE_ENCODE_H
 #define LOCOMOUSE_ENCODE_H
 
@@ -96,12 +114,27 @@ typedef struct {
 /* Worst case of one frame's file in bytes (above); -1 for sizes out of range. */
 int64_t lm_enc_slot_bytes(int32_t rows, int32_t cols, int32_t format);
 
+/* The same for a context with a restart interval of restart_interval MCUs
+ * (0..65535; 0 gives lm_enc_slot_bytes); -1 for arguments out of range. */
+int64_t lm_enc_slot_bytes_restart(int32_t rows, int32_t cols, int32_t format, int32_t restart_interval);
+
 /* An encoder for frames of rows x cols (1..65535 each, at most
  * LM_ENC_MAX_BLOCKS blocks) in `format`, at `quality` (1..100), at most
  * max_batch (1..LM_ENC_MAX_BATCH) frames per call, on HIP device `device`.
  * max_batch * lm_enc_slot_bytes must stay below 2^31. */
 lm_status lm_enc_create(int32_t device, int32_t rows, int32_t cols, int32_t format, int32_t quality, int32_t max_batch,
                         lm_enc_ctx** out);
+/* The same with restart intervals, as libjpeg writes them (restart_interval in
+ * MCUs, 0..65535): a DRI segment in front of SOS; after every restart_interval
+ * MCUs but the frame's last, the 1-bit fill to a byte boundary (stuffed like any
+ * other byte), the marker FF D0 + (j mod 8) for the j-th interval end, and DC
+ * predictors that start again from 0.  The files are host/JpegEncode.hpp's
+ * encode_jpeg with that restart_interval.  An interval of at least the frame's
+ * MCU count writes the DRI segment and no marker.  0 is lm_enc_create: the
+ * same files, buffers and kernels.  max_batch * lm_enc_slot_bytes_restart must
+ * stay below 2^31. */
+lm_status lm_enc_create_restart(int32_t device, int32_t rows, int32_t cols, int32_t format, int32_t quality,
+                                int32_t max_batch, int32_t restart_interval, lm_enc_ctx** out);
 void lm_enc_destroy(lm_enc_ctx* ctx);
 
 /* Encodes n <= max_batch frames: frame i at base + i * pitch, tightly packed

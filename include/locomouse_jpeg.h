@@ -86,6 +86,28 @@ lm_status lm_jpeg_upload(lm_jpeg_ctx* ctx, uint8_t* d_dst, const uint8_t* src, s
 void* lm_jpeg_stream(lm_jpeg_ctx* ctx); /* hipStream_t of the decode kernels */
 lm_status lm_jpeg_debug_stats(lm_jpeg_ctx* ctx, lm_jpeg_stats* out);
 
+/* The interval path.  A frame with a DRI segment and more than one restart
+ * interval is decoded one lane per interval: behind a restart marker the
+ * decoder's state is known and DC prediction starts again, so no lane guesses
+ * and none waits for another.  A frame whose markers are not exactly those its
+ * header asks for, or one of whose intervals does not decode cleanly into
+ * exactly its blocks, is handed to the subsequence path on the device, within
+ * the same call; statuses and pixels are the subsequence path's, always.
+ * lm_jpeg_set_interval_path switches the path (the default is on; the
+ * environment variable LM_JPEG_RST=0, read when the context is created, makes
+ * the default off): the A/B switch on one build. */
+lm_status lm_jpeg_set_interval_path(lm_jpeg_ctx* ctx, int32_t on);
+
+typedef struct lm_jpeg_interval_stats { /* the last lm_jpeg_decode_device call */
+  int32_t frames_interval;        /* frames the interval path decoded */
+  int32_t frames_handed_over;     /* restart frames it handed to the subsequence path (marker count, irregular lane) */
+  int64_t intervals;              /* lanes it ran, over all frames */
+  int32_t longest_interval_bytes; /* over those lanes */
+  int32_t reserved;
+  double parse_ms;                /* host: header parse of the batch, the marker index included */
+} lm_jpeg_interval_stats;
+lm_status lm_jpeg_debug_interval_stats(lm_jpeg_ctx* ctx, lm_jpeg_interval_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,17 @@ class lm_jpeg_stats(C.Structure):
     ]
 
 
+class lm_jpeg_interval_stats(C.Structure):
+    _fields_ = [
+        ("frames_interval", C.c_int32),
+        ("frames_handed_over", C.c_int32),
+        ("intervals", C.c_int64),
+        ("longest_interval_bytes", C.c_int32),
+        ("reserved", C.c_int32),
+        ("parse_ms", C.c_double),
+    ]
+
+
 def bb_params(median_filter_size=11, min_pixel_visible=1, moving_average_window=5, connectivity=8,
               semantics=LM_BB_FIRSTLAST_AS_EXECUTED, zero_cols=(46, 760), zero_rows=(100, 149), bb_width=400,
               bb_height_side=150):

@@ -6,6 +6,18 @@
 //                 time: guess, sync rounds, block-count prefix sum, final pass
 //                 (lm_jpeg_scan.h).  The last lane's settled exit state and the
 //                 block / restart counts carry into the next chunk.
+//   k_jpeg_scan_rst  the interval path, in front of k_jpeg_scan: one lane per
+//                 (frame, restart interval), flattened over the batch through
+//                 a per-frame exclusive offset table.  A lane starts behind its
+//                 marker from the known state, with no guess, sync round or
+//                 prefix sum, and must complete exactly its interval's blocks
+//                 (lmj_decode_interval).  The host builds the marker index while
+//                 lmj::parse walks the scan.  A frame whose index count is off,
+//                 or one of whose lanes is irregular, is flagged in device
+//                 memory; k_jpeg_scan returns at once for the other frames of
+//                 the path and decodes the flagged ones as if the path had not
+//                 run (it zeroes what the lanes wrote first), with no host round
+//                 trip.
 //   k_jpeg_dc     DC prediction: segmented prefix sum of the DC differences
 //                 per component, restarted at each restart interval.
 //   k_jpeg_idct   one thread per 8x8 block: dequantise + ISLOW IDCT into the
@@ -18,11 +30,16 @@
 // by the frame's block count (<= max_blk, the context's allocation), sync
 // rounds are bounded by the chunk's lanes, symbols by the bits of the
 // subsequence.  A damaged scan ends in error bits, which become
-// LM_JPEG_NEEDS_HOST.
+// LM_JPEG_NEEDS_HOST.  The interval path's lanes run the same loop between two
+// offsets of the marker index, which lmj_decode_interval checks against the
+// scan's length before a byte is read; the index is read at lanes below the
+// offset table's total only, and a lane's frame index is below n.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -49,9 +66,62 @@ struct JOut {
 
 static_assert(sizeof(LmjTableSet) % 4 == 0, "copied to LDS by dwords");
 
+// Per-frame flag of the interval path, in device memory.
+constexpr uint32_t kRstDone = 0;    // the interval path decodes the frame: k_jpeg_scan skips it
+constexpr uint32_t kRstNone = 1;    // not on the interval path: k_jpeg_scan decodes it, its buffers are clean
+constexpr uint32_t kRstFailed = 2;  // a lane of the interval path was irregular: k_jpeg_scan zeroes and decodes
+
+// ioff: n + 1 entries, the exclusive sum of the frames' interval counts (0 for a frame that is not on the path);
+// starts: ioff[n] entries, for each lane the byte of its frame's scan at which it starts (0, then the byte behind
+// each marker).  Lane g belongs to the frame f with ioff[f] <= g < ioff[f + 1].
+__global__ __launch_bounds__(LMJ_LANES) void k_jpeg_scan_rst(const JFrame* __restrict__ frames,
+                                                             const LmjTableSet* __restrict__ tsets, int16_t* coef_all,
+                                                             int32_t* dc_all, uint32_t max_blk,
+                                                             const uint32_t* __restrict__ ioff, int n,
+                                                             const uint32_t* __restrict__ starts, uint32_t* flag) {
+  __shared__ LmjTableSet T;
+  const int tid = threadIdx.x;
+  const uint32_t total = ioff[n];
+  const uint32_t g0 = blockIdx.x * (uint32_t)LMJ_LANES;
+  if (g0 >= total) return;  // uniform over the workgroup
+  auto frame_of = [&](uint32_t g) {  // g < total = ioff[n]
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (ioff[mid] <= g)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    return lo;
+  };
+  // the table set of the workgroup's first lane goes to LDS; a lane of a frame with another set reads global memory
+  const int32_t tset0 = frames[frame_of(g0)].tset;
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tsets + tset0);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&T);
+    for (uint32_t i = tid; i < sizeof(LmjTableSet) / 4; i += LMJ_LANES) dst[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t g = g0 + (uint32_t)tid;
+  if (g >= total) return;
+  const int f = frame_of(g);
+  const JFrame& F = frames[f];
+  LmjScan sc = F.sc;
+  if (sc.nblk > max_blk) sc.nblk = max_blk;  // (the host never asks for more)
+  const uint32_t j = g - ioff[f], nint = ioff[f + 1] - ioff[f];
+  const uint32_t start = starts[g], end = j + 1 < nint ? starts[g + 1] : sc.len;
+  int16_t* coef = coef_all + (uint64_t)f * max_blk * 64;
+  int32_t* dcd = dc_all + (uint64_t)f * max_blk;
+  const bool ok = F.active && (F.tset == tset0 ? lmj_decode_interval(sc, T, j, nint, start, end, coef, dcd)
+                                               : lmj_decode_interval(sc, tsets[F.tset], j, nint, start, end, coef, dcd));
+  if (!ok) atomicOr(&flag[f], kRstFailed);
+}
+
 __global__ __launch_bounds__(LMJ_LANES) void k_jpeg_scan(const JFrame* __restrict__ frames,
                                                          const LmjTableSet* __restrict__ tsets, int16_t* coef_all,
-                                                         int32_t* dc_all, uint32_t max_blk, JOut* out) {
+                                                         int32_t* dc_all, uint32_t max_blk, JOut* out,
+                                                         const uint32_t* __restrict__ flag) {
   __shared__ LmjTableSet T;
   __shared__ LmjState ex[LMJ_LANES];
   __shared__ uint32_t sblk[LMJ_LANES], srst[LMJ_LANES];
@@ -59,6 +129,8 @@ __global__ __launch_bounds__(LMJ_LANES) void k_jpeg_scan(const JFrame* __restric
   const int tid = threadIdx.x;
   const JFrame& F = frames[blockIdx.x];
   if (!F.active) return;  // uniform over the workgroup
+  const uint32_t fl = flag[blockIdx.x];
+  if (fl == kRstDone) return;  // the interval path finished this frame
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(tsets + F.tset);
     uint32_t* dst = reinterpret_cast<uint32_t*>(&T);
@@ -69,6 +141,11 @@ __global__ __launch_bounds__(LMJ_LANES) void k_jpeg_scan(const JFrame* __restric
   if (sc.nblk > max_blk) sc.nblk = max_blk;  // (the host never asks for more)
   int16_t* coef = coef_all + (uint64_t)blockIdx.x * max_blk * 64;
   int32_t* dcd = dc_all + (uint64_t)blockIdx.x * max_blk;
+  if (fl & kRstFailed) {  // what the interval path's lanes left: back to the zeroes this path starts from
+    uint4* c4 = reinterpret_cast<uint4*>(coef);  // (a frame's coefficients begin at a multiple of 128 bytes)
+    for (uint32_t i = tid; i < sc.nblk * 8u; i += LMJ_LANES) c4[i] = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = tid; i < sc.nblk; i += LMJ_LANES) dcd[i] = 0;
+  }
   __syncthreads();
 
   LmjState carry{0, 0, 0};
@@ -252,6 +329,12 @@ struct lm_jpeg_ctx {
   DevBuf<int32_t> d_dc;
   DevBuf<JOut> d_out;
   HostBuf<JOut> h_out;
+  // interval path: ioff (max_batch + 1 entries) then flag (max_batch) in one buffer; starts grows on demand
+  bool rst_on = true;
+  DevBuf<uint32_t> d_rst, d_starts;
+  HostBuf<uint32_t> h_rst, h_starts;
+  std::vector<uint32_t> index;  // one frame's marker index
+  lm_jpeg_interval_stats istats{};
   lm_jpeg_stats stats{};
   std::vector<std::unique_ptr<DevBuf<uint8_t>>> user;  // lm_jpeg_device_alloc
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -273,26 +356,59 @@ void jpeg_decode(lm_jpeg_ctx* c, const uint8_t* const* jpeg, const size_t* size,
   if (n < 0 || n > c->max_batch) throw std::invalid_argument("n exceeds the context's max_batch");
   if (pitch < (int64_t)c->rows * c->cols) throw std::invalid_argument("pitch is smaller than a frame");
   c->stats = lm_jpeg_stats{};
+  c->istats = lm_jpeg_interval_stats{};
   if (n == 0) return;
   HIPCHK(hipSetDevice(c->device));
   std::vector<lmj::Header> hdr((size_t)n);
   std::map<std::string, int> sets;  // identical table sets are uploaded once
   size_t total = 0;
   int n_active = 0;
+  // interval path: the lanes' start bytes, frame after frame (h_starts grows below, once the counts are known)
+  std::vector<uint32_t> starts;
+  uint32_t* h_ioff = c->h_rst.p;
+  uint32_t* h_flag = c->h_rst.p + c->max_batch + 1;
+  const auto t_parse = std::chrono::steady_clock::now();
   for (int i = 0; i < n; ++i) {
     if (!jpeg[i]) throw std::invalid_argument("jpeg[i] is NULL");
     lmj::Header& h = hdr[(size_t)i];
-    lmj::parse(jpeg[i], size[i], h);
+    lmj::parse(jpeg[i], size[i], h, c->rst_on ? &c->index : nullptr);  // the index: one more store per marker
     if (h.cls == lmj::kInScope && (h.H != c->rows || h.W != c->cols)) h.cls = lmj::kNeedsHost;
     if (h.cls == lmj::kInScope && h.scan_len > c->scan_limit) h.cls = lmj::kNeedsHost;
     status[i] = h.cls == lmj::kInScope ? LM_JPEG_OK : h.cls == lmj::kNeedsHost ? LM_JPEG_NEEDS_HOST : LM_JPEG_REJECTED;
     if (h.cls == lmj::kRejected && g_err.empty()) g_err = h.why;
+    h_ioff[i] = (uint32_t)starts.size();
+    h_flag[i] = kRstNone;
+    if (c->rst_on && h.cls == lmj::kInScope && h.restart > 0) {
+      const uint32_t expected = lmj_expected_rst(lmj::make_scan(h, (uint32_t)c->subseq));
+      if (expected > 0 && c->index.size() == expected) {  // one lane per interval
+        h_flag[i] = kRstDone;
+        starts.push_back(0);
+        uint32_t prev = 0;
+        for (uint32_t off : c->index) {
+          starts.push_back(off);
+          c->istats.longest_interval_bytes = std::max(c->istats.longest_interval_bytes, (int32_t)(off - 2 - prev));
+          prev = off;
+        }
+        c->istats.longest_interval_bytes =
+            std::max(c->istats.longest_interval_bytes, (int32_t)((uint32_t)h.scan_len - prev));
+      } else if (expected > 0) {
+        ++c->istats.frames_handed_over;  // a marker is missing, or one too many: the index count differs
+      }
+    }
     if (h.cls == lmj::kInScope) {
       total += (h.scan_len + 15) & ~(size_t)15;
       ++n_active;
     }
   }
+  h_ioff[n] = (uint32_t)starts.size();
+  c->istats.parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_parse).count();
   if (n_active) {
+    if (c->h_starts.n < starts.size()) {
+      const size_t cap = starts.size() + starts.size() / 2 + 1024;
+      c->h_starts.alloc(cap);
+      c->d_starts.alloc(cap);
+    }
+    if (!starts.empty()) std::memcpy(c->h_starts.p, starts.data(), sizeof(uint32_t) * starts.size());
     if (c->h_bytes.n < total) {
       const size_t cap = total + total / 2 + 4096;
       c->h_bytes.alloc(cap);
@@ -312,8 +428,8 @@ void jpeg_decode(lm_jpeg_ctx* c, const uint8_t* const* jpeg, const size_t* size,
         it = sets.emplace(key, id).first;
       }
       F.sc = lmj::make_scan(h, (uint32_t)c->subseq);
-      if (F.sc.nblk > c->max_blk) {
-        status[i] = LM_JPEG_NEEDS_HOST;
+      if (F.sc.nblk > c->max_blk) {  // (not reached: the frame has the context's size.  Its lanes, if any, see an
+        status[i] = LM_JPEG_NEEDS_HOST;  // inactive frame and only raise its flag)
         continue;
       }
       std::memcpy(c->h_bytes.p + off, jpeg[i] + h.scan_off, h.scan_len);
@@ -335,9 +451,18 @@ void jpeg_decode(lm_jpeg_ctx* c, const uint8_t* const* jpeg, const size_t* size,
     HIPCHK(hipMemsetAsync(c->d_coef.p, 0, sizeof(int16_t) * 64 * (size_t)c->max_blk * (size_t)n, st));
     HIPCHK(hipMemsetAsync(c->d_dc.p, 0, sizeof(int32_t) * (size_t)c->max_blk * (size_t)n, st));
     HIPCHK(hipMemsetAsync(c->d_out.p, 0, sizeof(JOut) * (size_t)n, st));
+    const uint32_t lanes = h_ioff[n];
+    uint32_t* d_ioff = c->d_rst.p;
+    uint32_t* d_flag = c->d_rst.p + c->max_batch + 1;
+    HIPCHK(hipMemcpyAsync(c->d_rst.p, c->h_rst.p, sizeof(uint32_t) * (2 * (size_t)c->max_batch + 1), hipMemcpyHostToDevice, st));
     const int W = c->cols, H = c->rows;
+    if (lanes) {
+      HIPCHK(hipMemcpyAsync(c->d_starts.p, c->h_starts.p, sizeof(uint32_t) * lanes, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_jpeg_scan_rst, dim3((lanes + LMJ_LANES - 1) / LMJ_LANES), dim3(LMJ_LANES), 0, st, c->d_frames.p,
+                         c->d_tsets.p, c->d_coef.p, c->d_dc.p, c->max_blk, d_ioff, n, c->d_starts.p, d_flag);
+    }
     hipLaunchKernelGGL(k_jpeg_scan, dim3((unsigned)n), dim3(LMJ_LANES), 0, st, c->d_frames.p, c->d_tsets.p, c->d_coef.p,
-                       c->d_dc.p, c->max_blk, c->d_out.p);
+                       c->d_dc.p, c->max_blk, c->d_out.p, d_flag);
     hipLaunchKernelGGL(k_jpeg_dc, dim3((unsigned)n), dim3(LMJ_DC_THREADS), 0, st, c->d_frames.p, c->d_coef.p, c->d_dc.p,
                        c->max_blk);
     hipLaunchKernelGGL(k_jpeg_idct, dim3((c->max_blk + 255) / 256, (unsigned)n), dim3(256), 0, st, c->d_frames.p,
@@ -346,13 +471,16 @@ void jpeg_decode(lm_jpeg_ctx* c, const uint8_t* const* jpeg, const size_t* size,
                        W, H, c->d_py.p, c->ysz, c->d_pc.p, c->csz, d_out, pitch);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(JOut) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (lanes) HIPCHK(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(c->ev1, st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     c->stats.device_ms = ms;
+    c->istats.intervals = lanes;
     for (int i = 0; i < n; ++i) {
       if (!c->h_frames.p[i].active) continue;
+      if (h_ioff[i + 1] > h_ioff[i]) ++(h_flag[i] == kRstDone ? c->istats.frames_interval : c->istats.frames_handed_over);
       const JOut& o = c->h_out.p[i];
       if (o.err) status[i] = LM_JPEG_NEEDS_HOST;
       c->stats.sync_rounds += o.rounds;
@@ -413,6 +541,10 @@ LM_API lm_status lm_jpeg_create(int32_t device, int32_t rows, int32_t cols, int3
     c->d_dc.alloc((size_t)c->max_blk * nb);
     c->d_out.alloc(nb);
     c->h_out.alloc(nb);
+    c->d_rst.alloc(2 * nb + 1);
+    c->h_rst.alloc(2 * nb + 1);
+    const char* env = std::getenv("LM_JPEG_RST");  // "0": the interval path is off by default (the A/B switch)
+    c->rst_on = !(env && std::strcmp(env, "0") == 0);
   });
   if (s != LM_OK) {
     delete c;
@@ -480,6 +612,18 @@ LM_API lm_status lm_jpeg_upload(lm_jpeg_ctx* ctx, uint8_t* d_dst, const uint8_t*
 }
 
 LM_API void* lm_jpeg_stream(lm_jpeg_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+
+LM_API lm_status lm_jpeg_set_interval_path(lm_jpeg_ctx* ctx, int32_t on) {
+  if (!ctx) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  ctx->rst_on = on != 0;
+  return LM_OK;
+}
+
+LM_API lm_status lm_jpeg_debug_interval_stats(lm_jpeg_ctx* ctx, lm_jpeg_interval_stats* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  *out = ctx->istats;
+  return LM_OK;
+}
 
 LM_API lm_status lm_jpeg_debug_stats(lm_jpeg_ctx* ctx, lm_jpeg_stats* out) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");

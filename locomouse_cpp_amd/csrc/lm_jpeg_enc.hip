@@ -18,13 +18,24 @@
 //   k_enc_write     one workgroup per frame: header, the stuffed stream (a prefix
 //                   sum of FF counts places every byte), the 1-bit fill, EOI
 //
+// A context with restart intervals (lm_enc_create_restart) launches the <true>
+// instantiations of k_enc_scan, k_enc_pack and k_enc_write: the bit
+// offsets are rounded up to a byte at every interval end and the DC prediction
+// starts again behind it, the pack writes the 1-bit fill, and the write puts
+// the unstuffed marker in front of the interval's first byte: byte k of the
+// unstuffed stream lands at k, plus the FF bytes in front of it, plus twice the
+// intervals that ended in front of it.
+//
 // Safety.  Per frame the coefficient buffer has nblk * 64 entries, the offsets
 // nblk, the unstuffed stream W = 52 * nblk + 1 words, and the batch's output
 // max_batch * slot bytes (locomouse_encode.h derives both).  The size
 // categories are clamped (lje_cat_dc / lje_cat_ac), so a block's codes are at
 // most 1660 bits whatever the coefficient buffer holds: the bit offsets stay
 // below 52 * 32 * nblk, every word index below W, and a file's size is at most
-// the slot.  Files are packed at the running sum of their sizes, which the sum
+// the slot.  With restart intervals W and the slot grow by the fills and the
+// markers (locomouse_encode.h derives that too), the marker index reads the
+// offsets of blocks (m + 1) * bpi for m below the marker count only, and those
+// are below nblk.  Files are packed at the running sum of their sizes, which the sum
 // of the slots bounds.  Frames are read at i * pitch + [0, frame bytes) for
 // i < n only; pitch, n, and every mark and calibration index are checked on the
 // host before anything is launched.
@@ -42,7 +53,8 @@
 
 static_assert(LM_ENC_GRAY8 == LJE_GRAY8 && LM_ENC_RGB24 == LJE_RGB24, "the header's formats are the core's");
 static_assert(LM_ENC_BLOCK_WORDS == LJE_BLOCK_WORDS && LM_ENC_MAX_HEADER == LJE_MAX_HEADER, "the header's sizes are the core's");
-static_assert((int64_t)LM_ENC_MAX_BLOCKS * LJE_BLOCK_WORDS * 32 < ((int64_t)1 << 31), "bit offsets fit 31 bits");
+static_assert(((int64_t)LM_ENC_MAX_BLOCKS * LJE_BLOCK_WORDS + LM_ENC_MAX_BLOCKS / 4 + 1) * 32 < ((int64_t)1 << 31),
+              "bit offsets fit 31 bits, with a fill byte for every block");
 
 namespace {
 
@@ -166,16 +178,65 @@ __device__ inline int32_t dc_pred(const int16_t* __restrict__ fcoef, const LjeGe
   return p < 0 ? 0 : (int32_t)fcoef[(size_t)p * 64];
 }
 
+// Restart intervals (RST).  The kernels that know about them are second
+// instantiations of k_enc_scan, k_enc_pack and k_enc_write, so a context
+// without restarts launches the code it always did (RstArgs<false> is empty).
+// Block b ends an interval when the next one begins with a marker.
+template <bool RST>
+struct RstArgs;
+template <>
+struct RstArgs<false> {
+  static constexpr uint32_t bpi = 0, nmark = 0, nblk = 0;
+  static constexpr const uint32_t* bit_off = nullptr;
+};
+template <>
+struct RstArgs<true> {
+  const uint32_t* bit_off;  // every frame's bit offsets (k_enc_write's marker index)
+  uint32_t nblk;
+  uint32_t bpi;    // blocks of an interval: restart_interval * bpm > 0
+  uint32_t nmark;  // markers of a frame: its intervals - 1
+};
+template <bool RST>
+__device__ inline int32_t dc_pred_of(const int16_t* __restrict__ fcoef, const LjeGeom& g, uint32_t b, uint32_t bpi) {
+  if (!RST) return dc_pred(fcoef, g, b);
+  const int64_t p = lje_dc_pred_block_rst(g, b, bpi / (uint32_t)g.bpm);
+  return p < 0 ? 0 : (int32_t)fcoef[(size_t)p * 64];
+}
+__device__ inline bool ends_interval(const LjeGeom& g, uint32_t b, uint32_t bpi) {
+  return (b + 1u) % bpi == 0u && b + 1u < g.nblk;
+}
+
 __device__ inline void load_ehuf(const LjeTables* __restrict__ T, uint32_t* s_e) {
   for (int i = threadIdx.x; i < 2 * LJE_EHUF_STRIDE; i += kThreads) s_e[i] = T->ehuf[i];
   __syncthreads();
 }
 
+// A run of blocks as the bit offsets see it with restart intervals: from the
+// position s in front of it, the position behind it is s + head when no block
+// of the run ends an interval, and roundup8(s + head) + rest when one does
+// (head: the bits up to the first interval end, which is rounded up to a whole
+// byte; everything behind it starts at a byte boundary, so rest does not depend
+// on s).  Runs combine associatively, which is all the scan needs.
+struct RstRun {
+  uint32_t head, rest, ends;
+};
+__device__ inline uint32_t roundup8(uint32_t v) { return (v + 7u) & ~7u; }
+__device__ inline RstRun rst_join(const RstRun& a, const RstRun& b) {
+  if (!a.ends) return {a.head + b.head, b.rest, b.ends};
+  return {a.head, b.ends ? roundup8(a.rest + b.head) + b.rest : a.rest + b.head, 1u};
+}
+__device__ inline uint32_t rst_behind(const RstRun& r, uint32_t s) {
+  return r.ends ? roundup8(s + r.head) + r.rest : s + r.head;
+}
+
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void k_enc_scan(const int16_t* __restrict__ coef, LjeGeom g,
                                                        const LjeTables* __restrict__ T, uint32_t* __restrict__ bit_off,
-                                                       uint32_t* __restrict__ bits) {
+                                                       uint32_t* __restrict__ bits, RstArgs<RST> rst) {
+  const uint32_t bpi = rst.bpi;
   __shared__ uint32_t s_e[2 * LJE_EHUF_STRIDE];
   __shared__ uint32_t s_scan[2][kThreads];
+  __shared__ uint32_t s_rest[RST ? 2 : 1][RST ? kThreads : 1], s_ends[RST ? 2 : 1][RST ? kThreads : 1];
   load_ehuf(T, s_e);
   const int16_t* fcoef = coef + (size_t)blockIdx.x * g.nblk * 64;
   uint32_t* foff = bit_off + (size_t)blockIdx.x * g.nblk;
@@ -185,29 +246,55 @@ __global__ __launch_bounds__(kThreads) void k_enc_scan(const int16_t* __restrict
     uint32_t len = 0;
     if (b < g.nblk) {
       const uint32_t* e = s_e + ((g.bpm == 6 && b % 6u >= 4u) ? LJE_EHUF_STRIDE : 0);
-      walk_block(fcoef + (size_t)b * 64, dc_pred(fcoef, g, b), e, [&](uint32_t, uint32_t l) { len += l; });
+      walk_block(fcoef + (size_t)b * 64, dc_pred_of<RST>(fcoef, g, b, bpi), e, [&](uint32_t, uint32_t l) { len += l; });
     }
     int cur = 0;
     s_scan[0][threadIdx.x] = len;
+    if (RST) {
+      s_rest[0][threadIdx.x] = 0;
+      s_ends[0][threadIdx.x] = (b < g.nblk && ends_interval(g, b, bpi)) ? 1u : 0u;
+    }
     __syncthreads();
-    for (int step = 1; step < kThreads; step <<= 1) {  // inclusive scan of the 256 lengths
-      uint32_t v = s_scan[cur][threadIdx.x];
-      if ((int)threadIdx.x >= step) v += s_scan[cur][threadIdx.x - step];
-      s_scan[cur ^ 1][threadIdx.x] = v;
+    for (int step = 1; step < kThreads; step <<= 1) {  // inclusive scan of the 256 lengths (RST: runs)
+      if (RST) {
+        RstRun v = {s_scan[cur][threadIdx.x], s_rest[cur][threadIdx.x], s_ends[cur][threadIdx.x]};
+        if ((int)threadIdx.x >= step) {
+          const int t = threadIdx.x - step;
+          v = rst_join(RstRun{s_scan[cur][t], s_rest[cur][t], s_ends[cur][t]}, v);
+        }
+        s_scan[cur ^ 1][threadIdx.x] = v.head;
+        s_rest[cur ^ 1][threadIdx.x] = v.rest;
+        s_ends[cur ^ 1][threadIdx.x] = v.ends;
+      } else {
+        uint32_t v = s_scan[cur][threadIdx.x];
+        if ((int)threadIdx.x >= step) v += s_scan[cur][threadIdx.x - step];
+        s_scan[cur ^ 1][threadIdx.x] = v;
+      }
       cur ^= 1;
       __syncthreads();
     }
-    if (b < g.nblk) foff[b] = carry + s_scan[cur][threadIdx.x] - len;
-    carry += s_scan[cur][kThreads - 1];
+    if (RST) {
+      // a block begins where the run of the blocks in front of it in this round ends
+      if (b < g.nblk) {
+        const int t = (int)threadIdx.x - 1;
+        foff[b] = t < 0 ? carry : rst_behind(RstRun{s_scan[cur][t], s_rest[cur][t], s_ends[cur][t]}, carry);
+      }
+      carry = rst_behind(RstRun{s_scan[cur][kThreads - 1], s_rest[cur][kThreads - 1], s_ends[cur][kThreads - 1]}, carry);
+    } else {
+      if (b < g.nblk) foff[b] = carry + s_scan[cur][threadIdx.x] - len;
+      carry += s_scan[cur][kThreads - 1];
+    }
     __syncthreads();  // s_scan is rewritten by the next round
   }
   if (threadIdx.x == 0) bits[blockIdx.x] = carry;
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void k_enc_pack(const int16_t* __restrict__ coef, LjeGeom g,
                                                        const LjeTables* __restrict__ T,
                                                        const uint32_t* __restrict__ bit_off, uint32_t* __restrict__ words,
-                                                       uint32_t wpf) {
+                                                       uint32_t wpf, RstArgs<RST> rst) {
+  const uint32_t bpi = rst.bpi;
   __shared__ uint32_t s_e[2 * LJE_EHUF_STRIDE];
   load_ehuf(T, s_e);
   const uint32_t b = blockIdx.x * kThreads + threadIdx.x;
@@ -222,7 +309,7 @@ __global__ __launch_bounds__(kThreads) void k_enc_pack(const int16_t* __restrict
   // in it) hold other blocks' bits: those are ORed in atomically, the words between are this block's alone.
   bool shared = true;
   const uint32_t* e = s_e + ((g.bpm == 6 && b % 6u >= 4u) ? LJE_EHUF_STRIDE : 0);
-  walk_block(fcoef + (size_t)b * 64, dc_pred(fcoef, g, b), e, [&](uint32_t code, uint32_t l) {
+  auto put = [&](uint32_t code, uint32_t l) {
     if (!l) return;
     acc |= (uint64_t)code << (64u - nacc - l);  // nacc <= 31 and l <= 16
     nacc += l;
@@ -238,9 +325,15 @@ __global__ __launch_bounds__(kThreads) void k_enc_pack(const int16_t* __restrict
       acc <<= 32;
       nacc -= 32u;
     }
-  });
+  };
+  walk_block(fcoef + (size_t)b * 64, dc_pred_of<RST>(fcoef, g, b, bpi), e, put);
+  if (RST && ends_interval(g, b, bpi)) {  // the interval's 1-bit fill: words begin at byte boundaries
+    const uint32_t pad = (8u - (nacc & 7u)) & 7u;
+    put((1u << pad) - 1u, pad);
+  }
   if (nacc && widx < wpf) atomicOr(fw + widx, (uint32_t)(acc >> 32));
 }
+
 
 // Byte k of a frame's unstuffed stream of `bits` bits (k below its byte count),
 // the last one filled up with 1-bits.
@@ -281,17 +374,24 @@ __global__ void k_enc_offsets(const uint32_t* __restrict__ size, int n, uint32_t
   }
 }
 
+// RST: nmark markers, marker m (from 0) in front of the byte at which block (m + 1) * bpi begins (its bit offset,
+// a whole number of bytes).  Every block has at least 4 bits, so these bytes differ and all lie below nbytes.
+// foff: the frame's bit offsets.
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void k_enc_write(const uint32_t* __restrict__ words, uint32_t wpf,
                                                         const uint32_t* __restrict__ bits,
                                                         const uint8_t* __restrict__ hdr, uint32_t hdr_len,
-                                                        const uint32_t* __restrict__ offset, uint8_t* __restrict__ out) {
+                                                        const uint32_t* __restrict__ offset, uint8_t* __restrict__ out,
+                                                        RstArgs<RST> rst) {
+  const uint32_t* foff = RST ? rst.bit_off + (size_t)blockIdx.x * rst.nblk : nullptr;
+  const uint32_t bpi = rst.bpi, nmark = rst.nmark;
   __shared__ uint32_t s_scan[2][kThreads];
   const uint32_t* fw = words + (size_t)blockIdx.x * wpf;
   const uint32_t nbits = bits[blockIdx.x], nbytes = (nbits + 7u) >> 3;
   uint8_t* o = out + offset[blockIdx.x];
   for (uint32_t i = threadIdx.x; i < hdr_len; i += kThreads) o[i] = hdr[i];
   o += hdr_len;
-  uint32_t carry = 0;  // FF bytes in front of this round
+  uint32_t carry = 0;  // FF bytes (RST: and marker bytes) in front of this round
   for (uint32_t base = 0; base < nbytes; base += kThreads * kWriteBytes) {
     const uint32_t k0 = base + threadIdx.x * kWriteBytes;
     uint32_t w[kWriteBytes / 4];
@@ -304,6 +404,20 @@ __global__ __launch_bounds__(kThreads) void k_enc_write(const uint32_t* __restri
 #pragma unroll
     for (uint32_t j = 0; j < kWriteBytes; ++j)
       if (k0 + j < nbytes && stream_byte(w[j >> 2], k0 + j, nbits) == 255u) ++ff;
+    uint32_t mark = 0;  // RST: the markers in front of byte k0
+    if (RST && k0 < nbytes) {
+      uint32_t lo = 0, hi = nmark;  // the first marker whose byte is not below k0
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((foff[(size_t)(mid + 1u) * bpi] >> 3) < k0)
+          lo = mid + 1u;
+        else
+          hi = mid;
+      }
+      mark = lo;
+      const uint32_t kend = k0 + kWriteBytes < nbytes ? k0 + kWriteBytes : nbytes;
+      for (uint32_t m = mark; m < nmark && (foff[(size_t)(m + 1u) * bpi] >> 3) < kend; ++m) ff += 2u;  // at most 16
+    }
     int cur = 0;
     s_scan[0][threadIdx.x] = ff;
     __syncthreads();
@@ -315,9 +429,16 @@ __global__ __launch_bounds__(kThreads) void k_enc_write(const uint32_t* __restri
       __syncthreads();
     }
     uint32_t pos = k0 + carry + s_scan[cur][threadIdx.x] - ff;
+    uint32_t next = (RST && k0 < nbytes && mark < nmark) ? foff[(size_t)(mark + 1u) * bpi] >> 3 : 0xFFFFFFFFu;
 #pragma unroll
     for (uint32_t j = 0; j < kWriteBytes; ++j) {
       if (k0 + j < nbytes) {
+        if (RST && k0 + j == next) {
+          o[pos++] = 0xFF;
+          o[pos++] = (uint8_t)(0xD0u + (mark & 7u));
+          ++mark;
+          next = mark < nmark ? foff[(size_t)(mark + 1u) * bpi] >> 3 : 0xFFFFFFFFu;
+        }
         const uint32_t v = stream_byte(w[j >> 2], k0 + j, nbits);
         o[pos++] = (uint8_t)v;
         if (v == 255u) o[pos++] = 0;
@@ -342,6 +463,7 @@ struct lm_enc_ctx {
   uint32_t wpf = 0;        // words of one frame's unstuffed stream
   size_t slot = 0;
   uint32_t hdr_len = 0;
+  uint32_t bpi = 0, nmark = 0;  // restart intervals: blocks per interval (0: none), markers per frame
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf<LjeTables> d_tables;
@@ -396,13 +518,30 @@ void encode_on_device(lm_enc_ctx* c, const uint8_t* d_frames, int64_t pitch, int
   HIPCHK(hipMemsetAsync(c->d_words.p, 0, sizeof(uint32_t) * (size_t)c->wpf * (size_t)n, c->stream));
   hipLaunchKernelGGL(k_enc_coef, dim3((g.nblk + kBlocksPerGroup - 1) / kBlocksPerGroup, n), dim3(kThreads), 0, c->stream,
                      d_frames, pitch, g, c->d_tables.p, c->d_coef.p);
-  hipLaunchKernelGGL(k_enc_scan, dim3(n), dim3(kThreads), 0, c->stream, c->d_coef.p, g, c->d_tables.p, c->d_off.p, d_bits);
-  hipLaunchKernelGGL(k_enc_pack, dim3((g.nblk + kThreads - 1) / kThreads, n), dim3(kThreads), 0, c->stream, c->d_coef.p, g,
-                     c->d_tables.p, c->d_off.p, c->d_words.p, c->wpf);
-  hipLaunchKernelGGL(k_enc_count, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits, c->hdr_len, d_size);
-  hipLaunchKernelGGL(k_enc_offsets, dim3(1), dim3(64), 0, c->stream, d_size, n, d_offs);
-  hipLaunchKernelGGL(k_enc_write, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits, c->d_hdr.p,
-                     c->hdr_len, d_offs, c->d_out.p);
+  const dim3 pack_grid((g.nblk + kThreads - 1) / kThreads, n);
+  if (c->bpi) {
+    const RstArgs<true> rst{c->d_off.p, g.nblk, c->bpi, c->nmark};
+    hipLaunchKernelGGL(k_enc_scan<true>, dim3(n), dim3(kThreads), 0, c->stream, c->d_coef.p, g, c->d_tables.p, c->d_off.p,
+                       d_bits, rst);
+    hipLaunchKernelGGL(k_enc_pack<true>, pack_grid, dim3(kThreads), 0, c->stream, c->d_coef.p, g, c->d_tables.p, c->d_off.p,
+                       c->d_words.p, c->wpf, rst);
+    // every frame has the same count of markers: k_enc_count takes their bytes with the header's
+    hipLaunchKernelGGL(k_enc_count, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits,
+                       c->hdr_len + 2u * c->nmark, d_size);
+    hipLaunchKernelGGL(k_enc_offsets, dim3(1), dim3(64), 0, c->stream, d_size, n, d_offs);
+    hipLaunchKernelGGL(k_enc_write<true>, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits, c->d_hdr.p,
+                       c->hdr_len, d_offs, c->d_out.p, rst);
+  } else {
+    const RstArgs<false> none{};
+    hipLaunchKernelGGL(k_enc_scan<false>, dim3(n), dim3(kThreads), 0, c->stream, c->d_coef.p, g, c->d_tables.p, c->d_off.p,
+                       d_bits, none);
+    hipLaunchKernelGGL(k_enc_pack<false>, pack_grid, dim3(kThreads), 0, c->stream, c->d_coef.p, g, c->d_tables.p,
+                       c->d_off.p, c->d_words.p, c->wpf, none);
+    hipLaunchKernelGGL(k_enc_count, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits, c->hdr_len, d_size);
+    hipLaunchKernelGGL(k_enc_offsets, dim3(1), dim3(64), 0, c->stream, d_size, n, d_offs);
+    hipLaunchKernelGGL(k_enc_write<false>, dim3(n), dim3(kThreads), 0, c->stream, c->d_words.p, c->wpf, d_bits, c->d_hdr.p,
+                       c->hdr_len, d_offs, c->d_out.p, none);
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev1, c->stream));
   // sizes and offsets (adjacent in d_meta), then exactly the files' bytes
@@ -465,13 +604,40 @@ LM_API int64_t lm_enc_slot_bytes(int32_t rows, int32_t cols, int32_t format) {
   return nblk < 0 ? -1 : LM_ENC_MAX_HEADER + 2 * 4 * (LM_ENC_BLOCK_WORDS * nblk + 1) + 2;
 }
 
+namespace {
+
+// Words of one frame's unstuffed stream with restart intervals (locomouse_encode.h derives it).
+int64_t words_restart(int64_t nblk, int64_t intervals) { return LM_ENC_BLOCK_WORDS * nblk + (intervals + 3) / 4 + 1; }
+
+int64_t intervals_of(int64_t nblk, int32_t format, int32_t restart_interval) {
+  const int64_t nmcu = nblk / (format == LM_ENC_RGB24 ? 6 : 1);
+  return (nmcu + restart_interval - 1) / restart_interval;
+}
+
+}  // namespace
+
+LM_API int64_t lm_enc_slot_bytes_restart(int32_t rows, int32_t cols, int32_t format, int32_t restart_interval) {
+  if (restart_interval < 0 || restart_interval > 65535) return -1;
+  if (restart_interval == 0) return lm_enc_slot_bytes(rows, cols, format);
+  const int64_t nblk = blocks_of(rows, cols, format);
+  if (nblk < 0) return -1;
+  const int64_t ni = intervals_of(nblk, format, restart_interval);
+  return LM_ENC_MAX_HEADER + 2 * 4 * words_restart(nblk, ni) + 2 * (ni - 1) + 2;
+}
+
 LM_API lm_status lm_enc_create(int32_t device, int32_t rows, int32_t cols, int32_t format, int32_t quality,
                                int32_t max_batch, lm_enc_ctx** out) {
+  return lm_enc_create_restart(device, rows, cols, format, quality, max_batch, 0, out);
+}
+
+LM_API lm_status lm_enc_create_restart(int32_t device, int32_t rows, int32_t cols, int32_t format, int32_t quality,
+                                       int32_t max_batch, int32_t restart_interval, lm_enc_ctx** out) {
   if (!out) return fail(LM_ERR_INVALID_ARGUMENT, "out is NULL");
   *out = nullptr;
   if (format != LM_ENC_GRAY8 && format != LM_ENC_RGB24) return fail(LM_ERR_INVALID_ARGUMENT, "format must be LM_ENC_GRAY8 or LM_ENC_RGB24");
   if (rows < 1 || cols < 1 || rows > 65535 || cols > 65535) return fail(LM_ERR_INVALID_ARGUMENT, "rows and cols must be in 1..65535");
-  const int64_t slot = lm_enc_slot_bytes(rows, cols, format);
+  if (restart_interval < 0 || restart_interval > 65535) return fail(LM_ERR_INVALID_ARGUMENT, "restart_interval must be in 0..65535");
+  const int64_t slot = lm_enc_slot_bytes_restart(rows, cols, format, restart_interval);
   if (slot < 0) return fail(LM_ERR_INVALID_ARGUMENT, "frame too large: more than LM_ENC_MAX_BLOCKS blocks");
   if (quality < 1 || quality > 100) return fail(LM_ERR_INVALID_ARGUMENT, "quality must be in 1..100");
   if (max_batch < 1 || max_batch > LM_ENC_MAX_BATCH) return fail(LM_ERR_INVALID_ARGUMENT, "max_batch must be in 1..LM_ENC_MAX_BATCH");
@@ -492,10 +658,16 @@ LM_API lm_status lm_enc_create(int32_t device, int32_t rows, int32_t cols, int32
     c->quality = quality;
     c->frame_bytes = (size_t)rows * (size_t)cols * (format == LM_ENC_RGB24 ? 3 : 1);
     c->wpf = (uint32_t)(LM_ENC_BLOCK_WORDS * c->g.nblk + 1);
+    if (restart_interval) {
+      const uint32_t ni = lje_intervals(c->g, (uint32_t)restart_interval);
+      c->bpi = (uint32_t)restart_interval * (uint32_t)c->g.bpm;
+      c->nmark = ni - 1;
+      c->wpf = (uint32_t)words_restart(c->g.nblk, ni);
+    }
     c->slot = (size_t)slot;
     LjeTables T;
     lje::make_tables(quality, T);
-    const std::vector<uint8_t> h = lje::header(rows, cols, format, quality);
+    const std::vector<uint8_t> h = lje::header(rows, cols, format, quality, restart_interval);
     if (h.size() > LM_ENC_MAX_HEADER) throw std::runtime_error("the JPEG header passed LM_ENC_MAX_HEADER");
     c->hdr_len = (uint32_t)h.size();
     c->d_tables.alloc(1);

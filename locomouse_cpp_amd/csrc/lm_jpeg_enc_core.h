@@ -36,7 +36,7 @@
 #define LJE_BLOCK_BITS 1660
 #define LJE_BLOCK_WORDS 52
 static_assert(LJE_BLOCK_WORDS * 32 >= LJE_BLOCK_BITS, "a block's worst case fits its words");
-#define LJE_MAX_HEADER 640  // SOI .. SOS of the colour layout is 623 bytes (lje::header checks it)
+#define LJE_MAX_HEADER 640  // SOI .. SOS of the colour layout is 623 bytes, 629 with a DRI segment (lje::header checks it)
 
 struct LjeGeom {
   int32_t rows, cols, format;
@@ -117,6 +117,21 @@ LJE_HD int64_t lje_dc_pred_block(const LjeGeom& g, uint32_t b) {
   if (j >= 1 && j <= 3) return (int64_t)b - 1;
   if (b < 6u) return -1;
   return j == 0 ? (int64_t)b - 3 : (int64_t)b - 6;  // Y3 of the MCU before; its Cb / Cr
+}
+
+// The same with a restart interval of ri > 0 MCUs (jchuff.c emit_restart): the
+// first MCU of an interval predicts every component from 0.
+LJE_HD int64_t lje_dc_pred_block_rst(const LjeGeom& g, uint32_t b, uint32_t ri) {
+  const uint32_t j = b % (uint32_t)g.bpm;
+  if (j >= 1 && j <= 3) return (int64_t)b - 1;
+  return (b / (uint32_t)g.bpm) % ri == 0 ? -1 : lje_dc_pred_block(g, b);
+}
+
+// Restart intervals of a scan of `ri` MCUs each (ri > 0): ceil(MCUs / ri).  All
+// but the last end in a marker.
+LJE_HD uint32_t lje_intervals(const LjeGeom& g, uint32_t ri) {
+  const uint32_t nmcu = g.nblk / (uint32_t)g.bpm;
+  return (nmcu + ri - 1) / ri;
 }
 
 // jccolor.c rgb_ycc_convert, 16 fractional bits.
@@ -285,8 +300,10 @@ inline void make_tables(int quality, LjeTables& T) {
   for (int k = 0; k < 64; ++k) T.pos[lmj::kNatural[k]] = (uint8_t)k;
 }
 
-// SOI .. SOS as libjpeg writes them for these settings (jcmarker.c).
-inline std::vector<uint8_t> header(int rows, int cols, int format, int quality) {
+// SOI .. SOS as libjpeg writes them for these settings (jcmarker.c).  A
+// restart interval > 0 (in MCUs, at most 65535) adds the DRI segment where
+// write_scan_header puts it: behind the DHT segments, in front of SOS.
+inline std::vector<uint8_t> header(int rows, int cols, int format, int quality, int restart_interval = 0) {
   std::vector<uint8_t> h = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
   const int nc = format == LJE_RGB24 ? 3 : 1, nt = nc == 3 ? 2 : 1;
   for (int t = 0; t < nt; ++t) {
@@ -313,6 +330,7 @@ inline std::vector<uint8_t> header(int rows, int cols, int format, int quality) 
     h.insert(h.end(), dht[t].bits, dht[t].bits + 16);
     h.insert(h.end(), dht[t].vals, dht[t].vals + n);
   }
+  if (restart_interval > 0) h.insert(h.end(), {0xFF, 0xDD, 0, 4, (uint8_t)(restart_interval >> 8), (uint8_t)restart_interval});
   h.insert(h.end(), {0xFF, 0xDA, 0, (uint8_t)(6 + 2 * nc), (uint8_t)nc});
   for (int c = 0; c < nc; ++c) h.insert(h.end(), {(uint8_t)(c + 1), (uint8_t)(c ? 0x11 : 0x00)});
   h.insert(h.end(), {0, 63, 0});

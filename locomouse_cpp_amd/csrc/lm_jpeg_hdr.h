@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "lm_jpeg_scan.h"
 
@@ -314,16 +315,24 @@ struct Header {
 // anything but 00 or D0..D7, or the end of the data.  (FF FF — a fill byte —
 // ends it too: the lanes then find too few blocks and the host decodes the
 // frame, whose reader skips fill bytes.)
-inline const uint8_t* scan_end(const uint8_t* p, const uint8_t* end) {
+// rst (may be null): the marker index of the segment, the offset from its
+// start of the byte behind each FF D0..D7, in order (the interval path of the
+// device decoder starts a lane at each).
+inline const uint8_t* scan_end(const uint8_t* p, const uint8_t* end, std::vector<uint32_t>* rst = nullptr) {
+  const uint8_t* const start = p;
   while (p < end) {
-    if (p[0] == 0xFF && p + 1 < end && p[1] != 0 && !(p[1] >= 0xD0 && p[1] <= 0xD7)) return p;
+    if (p[0] == 0xFF && p + 1 < end && p[1] != 0) {
+      if (!(p[1] >= 0xD0 && p[1] <= 0xD7)) return p;
+      if (rst) rst->push_back((uint32_t)(p + 2 - start));
+    }
     ++p;
   }
   return end;
 }
 
-inline void parse(const uint8_t* d, size_t n, Header& out) {
+inline void parse(const uint8_t* d, size_t n, Header& out, std::vector<uint32_t>* rst = nullptr) {
   out = Header();
+  if (rst) rst->clear();
   HeaderState<CompBase> S;
   bool seen = false;
   const char* host_why = nullptr;
@@ -344,7 +353,7 @@ inline void parse(const uint8_t* d, size_t n, Header& out) {
       out.v[c] = S.comp[c].v;
     }
     out.scan_off = (size_t)(p - d);
-    const uint8_t* e = scan_end(p, end);
+    const uint8_t* e = scan_end(p, end, rst);
     out.scan_len = (size_t)(e - p);
     const CompBase* C = S.comp;
     if (S.is_rgb()) host_why = "RGB (Adobe) colour space";

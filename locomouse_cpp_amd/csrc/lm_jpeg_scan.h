@@ -273,6 +273,35 @@ LMJ_HD uint32_t lmj_expected_rst(const LmjScan& sc) {
   return sc.restart && mcus ? (mcus - 1) / sc.restart : 0;
 }
 
+// ------------------------------------------------------------ interval path
+// A scan with restart markers needs no guess: behind RSTn the state is known
+// (a byte boundary, k = 0, b = 0) and DC prediction starts again, so every
+// restart interval decodes on its own.  Lane j of a frame with `nint`
+// intervals (lmj_expected_rst + 1) decodes the bytes [start, end): start is the
+// byte behind marker j - 1 (0 for lane 0), end the byte behind marker j (the
+// scan's length for the last lane), both from the marker index, which must
+// hold exactly lmj_expected_rst entries.  Its first block is j * restart * bpm.
+// It returns true when the lane completed exactly its blocks, cleanly: no error
+// bit, the block count of its interval, its one marker passed (none for the
+// last lane) at a block boundary.  Anything else hands the frame to the
+// subsequence path, which then decodes it as if this path had not run.
+// The loop is lmj_decode_subseq's, with its bit cap and bounds checks.
+LMJ_HD bool lmj_decode_interval(const LmjScan& sc, const LmjTableSet& T, uint32_t j, uint32_t nint, uint32_t start,
+                                uint32_t end, int16_t* coef, int32_t* dcdiff) {
+  if (sc.restart == 0 || j >= nint || start > end || end > sc.len) return false;
+  const uint64_t per = (uint64_t)sc.restart * sc.bpm, first = (uint64_t)j * per;
+  if (first >= sc.nblk) return false;
+  const uint32_t want = (uint32_t)(sc.nblk - first < per ? sc.nblk - first : per);
+  const bool last = j + 1 == nint;
+  LmjState s;
+  s.p = start * 8u;
+  s.k = 0;
+  s.b = 0;
+  LmjLane o;
+  s = lmj_decode_subseq<true>(sc, T, s, end * 8u, (uint32_t)first, j, coef, dcdiff, o);
+  return o.err == 0 && o.nblk == want && o.nrst == (last ? 0u : 1u) && s.k == 0 && s.b == 0;
+}
+
 // DC prediction restarts at block `blk` of the scan?
 LMJ_HD bool lmj_dc_reset(const LmjScan& sc, uint32_t blk) {
   return sc.restart && blk % (sc.restart * sc.bpm) == 0;
@@ -529,6 +558,26 @@ inline uint32_t lmj_scan_frame_host(const LmjScan& sc, const LmjTableSet& T, int
     st->err = err;
   }
   return err;
+}
+
+// The interval path's schedule on the CPU, lane by lane (k_jpeg_scan_rst).
+// rst: the scan's marker index (lmj::scan_end), nrst entries.  coef and dcdiff
+// as above, zeroed here.  Returns true when the path finished the frame; false
+// hands it to lmj_scan_frame_host: the index count differs from the expected
+// count, the frame has a single interval, or some lane did not complete exactly
+// its blocks.  (coef and dcdiff then hold what the lanes left: zero them again,
+// as lmj_scan_frame_host does.)
+inline bool lmj_scan_intervals_host(const LmjScan& sc, const LmjTableSet& T, const uint32_t* rst, uint32_t nrst,
+                                    int16_t* coef, int32_t* dcdiff) {
+  for (uint64_t i = 0; i < (uint64_t)sc.nblk * 64; ++i) coef[i] = 0;
+  for (uint32_t i = 0; i < sc.nblk; ++i) dcdiff[i] = 0;
+  const uint32_t expected = lmj_expected_rst(sc);
+  if (expected == 0 || nrst != expected) return false;
+  const uint32_t nint = expected + 1;
+  bool ok = true;
+  for (uint32_t j = 0; j < nint; ++j)  // every lane runs, as on the device
+    ok &= lmj_decode_interval(sc, T, j, nint, j ? rst[j - 1] : 0u, j + 1 < nint ? rst[j] : sc.len, coef, dcdiff);
+  return ok;
 }
 
 // DC prediction: per-component running sums of the differences, restarted at

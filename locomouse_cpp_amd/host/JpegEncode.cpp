@@ -48,17 +48,27 @@ void encode_jpeg_coefficients(const uint8_t* pixels, int rows, int cols, JpegInp
   for (uint32_t b = 0; b < g.nblk; ++b) lje::block_coefficients(pixels, g, T, b, coef.data() + (size_t)b * 64);
 }
 
-void encode_jpeg(const uint8_t* pixels, int rows, int cols, JpegInput format, int quality, std::vector<uint8_t>& out) {
+void encode_jpeg(const uint8_t* pixels, int rows, int cols, JpegInput format, int quality, std::vector<uint8_t>& out,
+                 int restart_interval) {
   check(pixels, rows, cols, quality);
+  if (restart_interval < 0 || restart_interval > 65535) throw std::invalid_argument("encode_jpeg: restart_interval must be in 0..65535");
   const LjeGeom g = lje_geom(rows, cols, (int)format);
   LjeTables T;
   lje::make_tables(quality, T);
-  const std::vector<uint8_t> h = lje::header(rows, cols, (int)format, quality);
+  const std::vector<uint8_t> h = lje::header(rows, cols, (int)format, quality, restart_interval);
   out.insert(out.end(), h.begin(), h.end());
   BitWriter w{out};
   int last_dc[3] = {0, 0, 0};
   int16_t c[64];
+  const uint32_t bpi = (uint32_t)restart_interval * (uint32_t)g.bpm;  // blocks of an interval
+  uint32_t marker = 0;
   for (uint32_t b = 0; b < g.nblk; ++b) {
+    if (bpi && b && b % bpi == 0) {  // jchuff.c emit_restart
+      w.flush();
+      out.push_back(0xFF);
+      out.push_back((uint8_t)(0xD0 + (marker++ & 7)));
+      last_dc[0] = last_dc[1] = last_dc[2] = 0;
+    }
     lje::block_coefficients(pixels, g, T, b, c);
     const int comp = lje_block(g, b).comp;
     const uint32_t* e = T.ehuf + (comp ? LJE_EHUF_STRIDE : 0);

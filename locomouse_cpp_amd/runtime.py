@@ -11,8 +11,8 @@ import subprocess
 import numpy as np
 
 from .abi import (BB_FRAME_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result, lm_enc_mark,
-                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_stats, lm_train_point,
-                  lm_train_stats, result_to_numpy)
+                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_interval_stats, lm_jpeg_stats,
+                  lm_train_point, lm_train_stats, result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -46,7 +46,8 @@ HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_
 
 # include/locomouse_jpeg.h (device MJPEG decode), same library
 JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
-                 "lm_jpeg_debug_stats", "lm_jpeg_device_alloc", "lm_jpeg_device_free", "lm_jpeg_upload")
+                 "lm_jpeg_debug_stats", "lm_jpeg_device_alloc", "lm_jpeg_device_free", "lm_jpeg_upload",
+                 "lm_jpeg_set_interval_path", "lm_jpeg_debug_interval_stats")
 
 # include/locomouse_bkg.h (the background as a per-pixel temporal median), same library
 BKG_EXPORTED = ("lm_bkg_create", "lm_bkg_destroy", "lm_bkg_push", "lm_bkg_push_device", "lm_bkg_finish",
@@ -54,8 +55,8 @@ BKG_EXPORTED = ("lm_bkg_create", "lm_bkg_destroy", "lm_bkg_push", "lm_bkg_push_d
 BKG_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseBackground")
 
 # include/locomouse_encode.h (device JPEG encode and the track overlay), same library
-ENC_EXPORTED = ("lm_enc_slot_bytes", "lm_enc_create", "lm_enc_destroy", "lm_enc_encode_device", "lm_enc_encode",
-                "lm_enc_set_overlay", "lm_enc_render_encode_device", "lm_enc_render_encode", "lm_enc_render_device", "lm_enc_stream",
+ENC_EXPORTED = ("lm_enc_slot_bytes", "lm_enc_slot_bytes_restart", "lm_enc_create", "lm_enc_create_restart", "lm_enc_destroy",
+                "lm_enc_encode_device", "lm_enc_encode", "lm_enc_set_overlay", "lm_enc_render_encode_device", "lm_enc_render_encode", "lm_enc_render_device", "lm_enc_stream",
                 "lm_enc_last_stats")
 
 # include/locomouse_train.h (detector weights trained from labelled patches), same library
@@ -63,6 +64,7 @@ TRAIN_EXPORTED = ("lm_train_create", "lm_train_destroy", "lm_train_add_patches",
                   "lm_train_gather_device", "lm_train_samples", "lm_train_reset", "lm_train_patches", "lm_train_solve",
                   "lm_train_margins", "lm_train_stream")
 TRAIN_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTrain")
+TRANSCODE_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTranscode")
 
 
 def _up_to_date(obj, cmd):
@@ -147,6 +149,12 @@ def build_host(verbose=False):
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
+    # LocoMouseTranscode: a video written again as grey MJPEG with restart markers (the device decoder's interval path)
+    cmd = [*flags, "-o", TRANSCODE_CLI_PATH, os.path.join(HOST_DIR, "TranscodeCli.cpp"), "-L" + PKG, "-llocomouse_host",
+           "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
     return HOST_LIB_PATH
 
 
@@ -216,6 +224,8 @@ def lib():
         L.lm_jpeg_stream.argtypes = [C.c_void_p]
         L.lm_jpeg_stream.restype = C.c_void_p
         L.lm_jpeg_debug_stats.argtypes = [C.c_void_p, C.POINTER(lm_jpeg_stats)]
+        L.lm_jpeg_set_interval_path.argtypes = [C.c_void_p, C.c_int32]
+        L.lm_jpeg_debug_interval_stats.argtypes = [C.c_void_p, C.POINTER(lm_jpeg_interval_stats)]
         L.lm_bkg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.lm_bkg_destroy.argtypes = [C.c_void_p]
         for fn in (L.lm_bkg_push, L.lm_bkg_push_device):
@@ -229,6 +239,10 @@ def lib():
         L.lm_enc_slot_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.lm_enc_slot_bytes.restype = C.c_int64
         L.lm_enc_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.lm_enc_slot_bytes_restart.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.lm_enc_slot_bytes_restart.restype = C.c_int64
+        L.lm_enc_create_restart.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(C.c_void_p)]
         L.lm_enc_destroy.argtypes = [C.c_void_p]
         for fn in (L.lm_enc_encode_device, L.lm_enc_encode):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(lm_enc_result)]
@@ -580,6 +594,16 @@ class JpegDecoder:
         _check(lib().lm_jpeg_debug_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in lm_jpeg_stats._fields_}
 
+    def set_interval_path(self, on):
+        """lm_jpeg_set_interval_path: restart-interval frames one lane per interval (the default), or every frame
+        through the subsequence path."""
+        _check(lib().lm_jpeg_set_interval_path(self._h, int(bool(on))))
+
+    def interval_stats(self):
+        s = lm_jpeg_interval_stats()
+        _check(lib().lm_jpeg_debug_interval_stats(self._h, C.byref(s)))
+        return {n: getattr(s, n) for n, _ in lm_jpeg_interval_stats._fields_ if n != "reserved"}
+
     def stream(self):
         return lib().lm_jpeg_stream(self._h)
 
@@ -739,21 +763,23 @@ class JpegEncoder:
     YCbCr 4:2:0) encoded as baseline JPEG files on one HIP device, byte for
     byte the host encoder's and libjpeg's (include/locomouse_encode.h); with
     set_overlay(), raw frames rendered through the calibration map with marks
-    drawn on them first."""
+    drawn on them first.  restart_interval (in MCUs, 0: none) writes libjpeg's
+    restart markers (lm_enc_create_restart)."""
 
     GRAY8, RGB24 = LM_ENC_GRAY8, LM_ENC_RGB24
 
-    def __init__(self, rows, cols, fmt=LM_ENC_GRAY8, quality=90, max_batch=64, device=0):
+    def __init__(self, rows, cols, fmt=LM_ENC_GRAY8, quality=90, max_batch=64, device=0, restart_interval=0):
         self._h = C.c_void_p()
-        _check(lib().lm_enc_create(device, rows, cols, fmt, quality, max_batch, C.byref(self._h)))
+        _check(lib().lm_enc_create_restart(device, rows, cols, fmt, quality, max_batch, restart_interval, C.byref(self._h)))
         self.rows, self.cols, self.fmt, self.quality = rows, cols, fmt, quality
+        self.restart_interval = restart_interval
         self.max_batch, self.device = max_batch, device
         self.frame_bytes = rows * cols * (3 if fmt == LM_ENC_RGB24 else 1)
         self._src = None
 
     @staticmethod
-    def slot_bytes(rows, cols, fmt):
-        return int(lib().lm_enc_slot_bytes(rows, cols, fmt))
+    def slot_bytes(rows, cols, fmt, restart_interval=0):
+        return int(lib().lm_enc_slot_bytes_restart(rows, cols, fmt, restart_interval))
 
     @staticmethod
     def _files(res):

@@ -36,6 +36,11 @@ annotated preview video) in turn on the same video, REPS times
 each, every repetition recorded; the runs without it are the baseline.
 
   python scripts/cli_e2e_mjpeg.py --preview --reps 3 --out profiles/r09/preview/e2e.json
+
+With --restart N the video's frames carry restart markers every N MCUs, which
+the device decoder takes through its interval path:
+
+  python scripts/cli_e2e_mjpeg.py --decode host,device --restart 8 --reps 3 --out profiles/rst/e2e.json
 """
 import argparse
 import json
@@ -126,6 +131,9 @@ def main():
                          "within each repetition on the same video, every repetition recorded")
     ap.add_argument("--preview", action="store_true",
                     help="one device, without and with LM_PREVIEW in turn within each repetition, every repetition recorded")
+    ap.add_argument("--restart", type=int, default=0,
+                    help="restart interval of the video's JPEG frames in MCUs (Pillow's restart_marker_blocks); with "
+                         "LM_DECODE=device such a video takes the decoder's interval path")
     a = ap.parse_args()
     from oracle import oracle as O
     cfg = S.SyntheticConfig()
@@ -134,10 +142,14 @@ def main():
     out = {"what": "LocoMouse program end to end: MJPEG AVI -> output_<stem>.yml", "frames": n,
            "video": f"{cfg.cols}x{cfg.rows} 4:2:0 colour MJPEG (Pillow/libjpeg-turbo, quality {a.quality})",
            "host_threads": threads}
+    if a.restart:
+        out["video"] += f", restart interval {a.restart} MCUs"
+        out["restart_mcus"] = a.restart
     with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as d:
         t0 = time.perf_counter()
         frames = O.synth_frames_c(cfg.rows, cfg.cols, 0, n)
-        js, dec = encode(frames, threads, mode="RGB", quality=a.quality, subsampling=2)
+        restart = dict(restart_marker_blocks=a.restart) if a.restart else {}
+        js, dec = encode(frames, threads, mode="RGB", quality=a.quality, subsampling=2, **restart)
         del frames
         paths = {k: os.path.join(d, v) for k, v in (("config", "config.yml"), ("video", "mouse_R.avi"),
                                                      ("background", "mouse_R.png"), ("model", "model.yml"),
