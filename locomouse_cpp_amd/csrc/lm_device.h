@@ -141,12 +141,16 @@ struct LmConst {
   // fit the LDS); tbw_inv[d]: lm_rcp of its tile columns.  The band's LDS:
   // block ranges (u16 max | min << 8 per ext row and block of the columns
   // tbw_blo[v] .. + tbw_nbk[v], both even; at most tbw_rows[v] rows) at 0,
-  // their four-row windows at tbw_v[v]; per detector P_i and N_i at
+  // their four-row windows at tbw_v[v] (which become their pair table in
+  // place -- entry b: the range over blocks b and b + 1, lm_tail_bound.h --
+  // when a detector of the view is refined; then the windows' entries at the
+  // last block of each detector's window, tbw_rows[v] per detector, at
+  // tbw_al[v]); per detector P_i and N_i at
   // tbw_pn[d], the window table (lm_tail_bound.h: wmax, then wmin at +
   // tbw_wsz[d]) at tbw_win[d], the list entries of the band at tbw_ent[d];
   // the tiles to evaluate at tbw_work[v].  All byte offsets; tbw_lds[v] bytes
   // in all.
-  int32_t tbw_br[2], tbw_nband[2], tbw_blo[2], tbw_nbk[2], tbw_rows[2], tbw_v[2], tbw_work[2], tbw_lds[2];
+  int32_t tbw_br[2], tbw_nband[2], tbw_blo[2], tbw_nbk[2], tbw_rows[2], tbw_v[2], tbw_al[2], tbw_work[2], tbw_lds[2];
   int32_t tbw_use[LM_NDET], tbw_pn[LM_NDET], tbw_win[LM_NDET], tbw_wsz[LM_NDET], tbw_ent[LM_NDET];
   uint32_t tbw_inv[LM_NDET];
   // the refinement per output block and tap group (lm_tail_bound.h) of the

@@ -681,6 +681,12 @@ static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the d
 #ifndef LM_TBW_LD
 #define LM_TBW_LD 8  // k_tile_bound: a thread's loads of block ranges in flight
 #endif
+#ifndef LM_TBW_CV
+#define LM_TBW_CV 8  // k_tile_bound: words of the pair table a thread forms between two barriers
+#endif
+#ifndef LM_TBW_CR
+#define LM_TBW_CR 2  // k_tile_bound: entries a thread holds while the refined entries close up
+#endif
 __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
     const LmConst* __restrict__ Kp, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes, int s0,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
@@ -845,17 +851,19 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
 //   4. lm_tb_tile_skip_win per listed tile: kh pairs of bytes, the work list
 //      handed out densely.  Kept tiles take their place in the band's entries
 //      by a ballot and one LDS atomic per wave.
-//   4b. The refinement of the kept tiles, one pass per detector over (tile,
-//      output block) pairs (see there); the entries of proven tiles drop out.
+//   4b. The refinement of the kept tiles: one pass over the (tile, output
+//      block) items of all three detectors, in wave-sized chunks of one
+//      detector each, the terms read from the pair table that the four-row
+//      windows are turned into after step 3 (3b: entry b is the range over
+//      blocks b and b + 1, which is what a term reads; see there);
+//      one compaction then drops the entries of proven tiles from all three
+//      segments.
 //   5. One global atomic per (workgroup, detector) on the slot group's segment
 //      counter (the segment index comes from the slot and the batch's slot
 //      count nslot, so all bands of a slot append to one segment), then the
 //      entries are copied out.
 // No index of a loop is divided at run time (lm_div by reciprocals).
-DEV uint32_t range_merge(uint32_t a, uint32_t b) {  // of two words of block ranges: max of bytes 0, 2, min of bytes 1, 3
-  return max(a & 0xFFu, b & 0xFFu) | min(a & 0xFF00u, b & 0xFF00u) | max(a & 0xFF0000u, b & 0xFF0000u) |
-         min(a & 0xFF000000u, b & 0xFF000000u);
-}
+DEV uint32_t range_merge(uint32_t a, uint32_t b) { return lm_tb_range_merge(a, b); }  // of two words of block ranges
 // The place of each lane with p set in the sequence counted by *ctr (LDS): one
 // atomic per wave.  To be called by whole waves.
 DEV int wave_append(bool p, int* ctr) {
@@ -995,6 +1003,18 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   // 3. the detectors' window tables
   const uint16_t* B16 = reinterpret_cast<const uint16_t*>(B);
   const uint16_t* V16 = reinterpret_cast<const uint16_t*>(V);
+  // (and, for the refinement, per detector the windows' entries at the last
+  // block of its window, which a term there reads alone: the windows
+  // themselves become their pair table below)
+  uint16_t* AL = reinterpret_cast<uint16_t*>(tbw_lds + K.tbw_al[v]);
+  const int nvr = max(nrow - (LM_TB_H - 1), 0), als = K.tbw_rows[v];  // window rows; the stride of a detector's entries
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (!refine[k]) continue;
+    const LmDet& D = K.det[3 * v + k];
+    const int bl = lm_tbr_block_end(D.in_x, D.ow, D.kw, K.ext_w[v] / LM_TB_BLK) - K.tbw_blo[v] - 1;
+    for (int r = tid; r < nvr; r += T) AL[k * als + r] = V16[r * nbk + bl];
+  }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     if (!use[k]) continue;
@@ -1027,6 +1047,33 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     }
   }
   __syncthreads();
+  // 3b. the windows become their pair table in place (entry b: the range over
+  // blocks b and b + 1, lm_tbr_pair_word: what a term of the refinement
+  // reads): a group of words is formed in registers, then written (a word
+  // needs its right neighbour as it was; a later group's words are not written
+  // before its own barrier).  Nothing reads the windows between here and 4b.
+  if (refine[0] || refine[1] || refine[2]) {
+    constexpr int CV = LM_TBW_CV;
+    const int nv = nvr * nw;
+    for (int e0 = 0; e0 < nv; e0 += CV * T) {
+      uint32_t pv[CV];
+#pragma unroll
+      for (int u = 0; u < CV; ++u) {
+        const int e = e0 + u * T + tid;
+        if (e < nv) {
+          const int r = lm_div(e, rc);
+          const bool last = e - r * nw == nw - 1;
+          pv[u] = lm_tbr_pair_word(V[e], last ? 0u : V[e + 1], last);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < CV; ++u) {
+        const int e = e0 + u * T + tid;
+        if (e < nv) V[e] = pv[u];
+      }
+    }
+  }
   // 4. the bound per tile of the work list
   int kh3[3], win3[3], wsz3[3], pn3[3];
   uint32_t inv3[3];
@@ -1070,63 +1117,101 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   }
   __syncthreads();
   // 4b. the refinement of the tiles the tile bound failed, which now stand in
-  // the band's entries: one pass per detector, so that kh, the group count and
-  // the constants (scalar loads of tbc, a 64-byte chunk of four groups at a
-  // time) are uniform; one (tile, output block) per thread.  A block is tried
-  // over the tile's four rows first (V), then row by row (B) at LM_TB_RH 1 (or
-  // over the rows of a short last tile row); a tile with a block that stays
-  // unproven is marked and keeps its entry, the others get flag 0 and the
-  // entries close up.
-  uint32_t* mark = work;  // (the work list is done with)
+  // the band's entries: one pass over the (tile, output block) items of all
+  // three detectors.  A detector's items are cut into chunks of a wave's lanes
+  // and the chunks of all detectors are handed to the waves in turn, so the
+  // lanes are dense and the detector is uniform in a wave: kh, the group count
+  // and the constants (scalar loads of tbc, a 64-byte chunk of four groups at
+  // a time, the next chunk fetched while this one is summed) stay scalar.  A
+  // block is tried over the tile's four rows first: a term reads one entry of
+  // the windows' pair table (V since 3b), a chunk's four entries as three words, the
+  // next chunk's words fetched before this chunk's terms are summed (after the
+  // last chunk: the row below, which the table's spare row covers); at the
+  // block the detector's window ends in, the term reads V (that block alone).  Then row by row (B)
+  // at LM_TB_RH 1 (or over the rows of a short last tile row), the pairs formed
+  // from B.  A tile with a block that stays unproven is marked and keeps its
+  // entry, the others get flag 0 and the entries of each detector close up.
+  uint32_t* mark = work;  // (the work list is done with; one word per entry, the detectors' one after the other)
+  int nr3[3], ent3[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    if (!refine[k]) continue;
-    const int n = __builtin_amdgcn_readfirstlane(s_n[k]);
-    if (n == 0) continue;
-    const int d = 3 * v + k;
-    const LmDet& D = K.det[d];
-    uint32_t* ent = reinterpret_cast<uint32_t*>(tbw_lds + K.tbw_ent[d]);
-    for (int t = tid; t < n; t += T) mark[t] = 0u;
+    nr3[k] = refine[k] ? __builtin_amdgcn_readfirstlane(s_n[k]) : 0;
+    ent3[k] = K.tbw_ent[3 * v + k];
+  }
+  const int nref = nr3[0] + nr3[1] + nr3[2];
+#define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
+  if (nref > 0) {
+    for (int t = tid; t < nref; t += T) mark[t] = 0u;
     __syncthreads();
-    const int kh = D.kh, ng = K.tbr_ng[d];
-    const double* __restrict__ C = tbc + K.tbr_off[d];
-    const double bias = K.tb_bias[d];
-    const int yb = D.in_y + LM_FH * t0[k] - y_lo;  // the band's window row 0 among the loaded rows
-    const int bl0 = lm_tbr_block0(D.in_x, 0) - K.tbw_blo[v];
-    const int bendl = lm_tbr_block_end(D.in_x, D.ow, D.kw, K.ext_w[v] / LM_TB_BLK) - K.tbw_blo[v];
-    const int nbx = (D.ow + LM_TB_BLK - 1) / LM_TB_BLK;
-    const uint32_t rcx = lm_rcp(LM_TB_NBX), rct = K.tbw_inv[d];
-    for (int e0 = 0; e0 < n * LM_TB_NBX; e0 += T) {
-      const int e = e0 + tid;
+    constexpr int WV = 64;  // lanes of a wave
+    const int c1 = (nr3[0] * LM_TB_NBX + WV - 1) / WV, c2 = c1 + (nr3[1] * LM_TB_NBX + WV - 1) / WV,
+              c3 = c2 + (nr3[2] * LM_TB_NBX + WV - 1) / WV;
+    const uint32_t rcx = lm_rcp(LM_TB_NBX);
+    for (int ch = __builtin_amdgcn_readfirstlane(tid / WV); ch < c3; ch += T / WV) {
+      const int k = ch < c1 ? 0 : ch < c2 ? 1 : 2;  // (uniform)
+      const int d = 3 * v + k;
+      const LmDet& D = K.det[d];
+      const int n = TBW_SEL(nr3), fx = TBW_SEL(ftx), tk0 = TBW_SEL(t0), ohk = TBW_SEL(ohb);
+      const int e = (ch - (k == 0 ? 0 : k == 1 ? c1 : c2)) * WV + (tid & (WV - 1));
+      const int mb = k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1];
+      const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + K.tbw_ent[d]);
+      const int kh = D.kh, ng = K.tbr_ng[d], nc = lm_tbr_chunks(ng);
+      const double* __restrict__ C = tbc + K.tbr_off[d];
+      const double bias = K.tb_bias[d];
+      const int yb = D.in_y + LM_FH * tk0 - y_lo;  // the band's window row 0 among the loaded rows
+      const int bl0 = lm_tbr_block0(D.in_x, 0) - K.tbw_blo[v];
+      const int bendl = lm_tbr_block_end(D.in_x, D.ow, D.kw, K.ext_w[v] / LM_TB_BLK) - K.tbw_blo[v];
+      const int nbx = (D.ow + LM_TB_BLK - 1) / LM_TB_BLK;
       if (e >= n * LM_TB_NBX) continue;
       const int t = lm_div(e, rcx);
       const int tile = (int)(ent[t] & 0xFFFFu);
-      const int ty = lm_div(tile, rct), tx = tile - ty * ftx[k];
+      const int ty = lm_div(tile, K.tbw_inv[d]), tx = tile - ty * fx;
       const int xb = tx * LM_TB_NBX + (e - t * LM_TB_NBX);
       if (xb >= nbx) continue;  // (a last tile column of fewer blocks)
-      const int tyb = ty - t0[k];
-      const int nr = min(LM_TB_H, ohb[k] - LM_TB_H * tyb);
+      const int tyb = ty - tk0;
+      const int nr = min(LM_TB_H, ohk - LM_TB_H * tyb);
       const int row0 = yb + LM_TB_H * tyb, ba0 = bl0 + xb;
-      // the tile's four rows at once from their windows V; rows rs .. rs + nn - 1 from the block ranges B
+      // the tile's four rows at once from the pair table of their windows
       auto level_v = [&]() {
+        const uint32_t* pw = V + row0 * nw + (ba0 >> 1);
+        const uint16_t* alone = AL + k * als + row0;  // the windows' last block of the detector's window, alone:
+        const bool clipped = ba0 + ng == bendl;       // what the last group reads when it stands there
+        const int jl = (ng - 1) % LM_TBR_GC;
+        uint32_t w0, w1, w2, x0 = 0u, x1 = 0u;
+        unsigned qn, q = 0u;
+        bool lastc = false;
+        auto fetch = [&]() {
+          w0 = pw[0];
+          w1 = pw[1];
+          w2 = pw[2];
+          qn = *alone;
+        };
+        fetch();
         return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
-          const int ba = ba0 + g, bb = min(ba + 1, bendl - 1);
-          const uint16_t* row = V16 + (row0 + i) * nbk;
-          const unsigned qa = row[ba], qb = row[bb];
-          M = max(qa & 0xFFu, qb & 0xFFu);
-          m = min(qa >> 8, qb >> 8);
+          if (g % LM_TBR_GC == 0) {  // a chunk's first term: its entries, and the next chunk's words on their way
+            const int c = g / LM_TBR_GC;
+            lm_tbr_quad_align(w0, w1, w2, ba0, x0, x1);
+            q = qn;
+            lastc = c == nc - 1;
+            // (after the last chunk the words of the row below, which the tables' spare row covers: no branch)
+            pw += lastc ? nw - 2 * (nc - 1) : 2;
+            alone += lastc ? 1 : 0;
+            fetch();
+          }
+          lm_tbr_quad_get(x0, x1, g % LM_TBR_GC, lastc && clipped && g % LM_TBR_GC == jl, q, M, m);
         });
       };
+      // rows rs .. rs + nn - 1 from the block ranges B
       auto level_b = [&](int rs, int nn) {
         return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
-          const int ba = ba0 + g, bb = min(ba + 1, bendl - 1);
           const uint16_t* row = B16 + (row0 + rs + i) * nbk;
           M = 0u;
           m = 255u;
           for (int r = 0; r < nn; ++r, row += nbk) {
-            const unsigned qa = row[ba], qb = row[bb];
-            M = max(M, max(qa & 0xFFu, qb & 0xFFu));
-            m = min(m, min(qa >> 8, qb >> 8));
+            unsigned a, b;
+            lm_tbr_pair_range(nullptr, row, ba0 + g, bendl, a, b);
+            M = max(M, a);
+            m = min(m, b);
           }
         });
       };
@@ -1139,22 +1224,45 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
           for (int r = 0; r < nr && proven; ++r) proven = level_b(r, 1);
         }
       }
-      if (!proven) mark[t] = 1u;
+      if (!proven) mark[mb + t] = 1u;
     }
     __syncthreads();
-    for (int c0 = 0; c0 < n; c0 += T) {  // (a chunk's entries are read before any of them is overwritten)
-      const int t = c0 + tid;
-      const bool act = t < n;
-      const uint32_t e = act ? ent[t] : 0u;
-      const bool kp = act && mark[t] != 0u;
-      if (act) fl[k][e & 0xFFFFu] = kp ? 1 : 0;
+    // the marked entries of each detector close up: a group of entries is read
+    // into registers, then written (an entry moves down or stays, and a later
+    // group's entries lie above every place written before, so one barrier per
+    // group of LM_TBW_CR * T entries, which a band's entries rarely exceed)
+    constexpr int CR = LM_TBW_CR;
+    for (int g0 = 0; g0 < nref; g0 += CR * T) {
+      uint32_t en[CR];
+      int kk[CR];
+#pragma unroll
+      for (int u = 0; u < CR; ++u) {
+        const int i = g0 + u * T + tid;
+        const bool act = i < nref;
+        const int k = i < nr3[0] ? 0 : i < nr3[0] + nr3[1] ? 1 : 2;
+        const int t = i - (k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]);
+        en[u] = act ? reinterpret_cast<const uint32_t*>(tbw_lds + TBW_SEL(ent3))[t] : 0u;
+        const bool kp = act && mark[i] != 0u;
+        kk[u] = kp ? k : -1;
+        if (act) TBW_SEL(fl)[en[u] & 0xFFFFu] = kp ? 1 : 0;
+      }
       __syncthreads();
-      const int pos = wave_append(kp, &s_m[k]);
-      if (kp) ent[pos] = e;
+#pragma unroll
+      for (int u = 0; u < CR; ++u)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const bool mine = kk[u] == k;
+          const int pos = wave_append(mine, &s_m[k]);
+          if (mine) reinterpret_cast<uint32_t*>(tbw_lds + ent3[k])[pos] = en[u];
+        }
     }
     __syncthreads();
-    if (tid == 0) s_n[k] = s_m[k];
+    if (tid < 3) {
+      const int k = tid;
+      if (TBW_SEL(nr3) > 0) s_n[k] = s_m[k];
+    }
   }
+#undef TBW_SEL
   __syncthreads();
   // 5. this workgroup's list segments and their counters, as in k_ingest
   const int G = (nslot + LM_INGEST_FB - 1) / LM_INGEST_FB;

@@ -824,6 +824,14 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
         int64_t o = 2 * (int64_t)K.tbw_rows[v] * K.tbw_nbk[v];
         K.tbw_v[v] = (int32_t)o;
         o += 2 * (int64_t)std::max(0, K.tbw_rows[v] - (LM_TB_H - 1)) * K.tbw_nbk[v];
+        // when a detector of the view is refined, the windows become their pair table (lm_tbr_pair_word) in place:
+        // a spare row and three words behind them (a term's words are fetched a chunk ahead, without a clamp), and
+        // per detector the windows' entries at the last block of its window (tbw_rows entries each: one spare)
+        bool pairs = false;
+        for (int k = 0; k < 3; ++k) pairs = pairs || (use[k] && K.tbr_on[3 * v + k] != 0);
+        if (pairs) o += 2 * (int64_t)K.tbw_nbk[v] + 16;
+        K.tbw_al[v] = (int32_t)o;
+        if (pairs) o += 2 * 3 * (int64_t)K.tbw_rows[v];
         o = (o + 7) / 8 * 8;
         for (int k = 0; k < 3; ++k) {
           const int d = 3 * v + k;

@@ -2,10 +2,11 @@
  * lm_tail_bound.h — an upper bound on a detector's scores over one 40 x 4
  * output tile, from per-row pixel ranges (plain C++: the host runtime, the
  * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
- * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp and
- * tests/cpp/tile_refine_check.cpp share it), and its refinement per 8-column
- * output block and tap group (below, lm_tbr_*).  Written for the tail
- * detectors (hence the name); it serves the point detectors too.
+ * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp,
+ * tests/cpp/tile_refine_check.cpp and tests/cpp/tile_pair_check.cpp share it),
+ * and its refinement per 8-column output block and tap group (below,
+ * lm_tbr_*).  Written for the tail detectors (hence the name); it serves the
+ * point detectors too.
  *
  * The pipeline uses only the sign of a tail score (threshold(> 0), then
  * connected components), and k_ingest zeroes the tail bitmaps, so a tile
@@ -280,27 +281,49 @@ LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double
   static_assert(LM_TBR_GC == 4, "a chunk is read as four P and four N");
   const int nc = lm_tbr_chunks(ng);
   double U = bias;
-  for (int i = 0; i < kh; ++i)
-    for (int c = 0; c < nc; ++c) {
-      const double* q = C + (i * nc + c) * 2 * LM_TBR_GC;
-      const double p0 = q[0], p1 = q[1], p2 = q[2], p3 = q[3], n0 = q[4], n1 = q[5], n2 = q[6], n3 = q[7];
-      const int g = c * LM_TBR_GC;
-      unsigned M, m;
-      rng(i, g, M, m);
-      U += p0 * (double)M - n0 * (double)m;
-      if (g + 1 < ng) {
-        rng(i, g + 1, M, m);
-        U += p1 * (double)M - n1 * (double)m;
-      }
-      if (g + 2 < ng) {
-        rng(i, g + 2, M, m);
-        U += p2 * (double)M - n2 * (double)m;
-      }
-      if (g + 3 < ng) {
-        rng(i, g + 3, M, m);
-        U += p3 * (double)M - n3 * (double)m;
-      }
+  // the terms of chunk c of row i, in order; ahead(): the fetch of the next
+  // chunk's constants, issued behind this chunk's first ranges (which a
+  // kernel has waited for by then) and ahead of its sums
+  auto chunk = [&](int i, int c, double p0, double p1, double p2, double p3, double n0, double n1, double n2, double n3,
+                   auto&& ahead) {
+    const int g = c * LM_TBR_GC, nt = ng - g;
+    unsigned M, m;
+    rng(i, g, M, m);
+    ahead();
+    U += p0 * (double)M - n0 * (double)m;
+    if (nt > 1) {
+      rng(i, g + 1, M, m);
+      U += p1 * (double)M - n1 * (double)m;
     }
+    if (nt > 2) {
+      rng(i, g + 2, M, m);
+      U += p2 * (double)M - n2 * (double)m;
+    }
+    if (nt > 3) {
+      rng(i, g + 3, M, m);
+      U += p3 * (double)M - n3 * (double)m;
+    }
+  };
+  // The chunks of all rows are contiguous and taken two at a time: a chunk's
+  // constants are fetched while the chunk before it is summed, into the
+  // registers of the chunk before that.
+  const double* q = C;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0;
+  double b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0, b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+  int i = 0, c = 0;
+  if (kh * nc > 0) a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5], a6 = q[6], a7 = q[7];
+  for (int left = kh * nc; left > 0; left -= 2, q += 4 * LM_TBR_GC) {
+    chunk(i, c, a0, a1, a2, a3, a4, a5, a6, a7, [&] {
+      if (left > 1) b0 = q[8], b1 = q[9], b2 = q[10], b3 = q[11], b4 = q[12], b5 = q[13], b6 = q[14], b7 = q[15];
+    });
+    if (++c == nc) c = 0, ++i;
+    if (left > 1) {
+      chunk(i, c, b0, b1, b2, b3, b4, b5, b6, b7, [&] {
+        if (left > 2) a0 = q[16], a1 = q[17], a2 = q[18], a3 = q[19], a4 = q[20], a5 = q[21], a6 = q[22], a7 = q[23];
+      });
+      if (++c == nc) c = 0, ++i;
+    }
+  }
   return U < 0.0;
 }
 // First block (of the view's) that output block xb reads at group 0, and the
@@ -329,6 +352,60 @@ LM_TB_HD inline bool lm_tbr_block_skip(const uint8_t* bmax, const uint8_t* bmin,
     }
   });
 }
+// ------------------------------------------------------------------------
+// Range tables as k_tile_bound keeps them: one 16-bit entry M | m << 8 per
+// (row, block), two entries (blocks 2 w and 2 w + 1) per 32-bit word, an even
+// number nbk of blocks per row.  lm_tb_range_merge: the range over two words'
+// blocks, entry by entry (the largest of bytes 0 and 2, the smallest of bytes
+// 1 and 3).
+LM_TB_HD inline uint32_t lm_tb_range_merge(uint32_t a, uint32_t b) {
+  const uint32_t a0 = a & 0xFFu, b0 = b & 0xFFu, a1 = a & 0xFF00u, b1 = b & 0xFF00u;
+  const uint32_t a2 = a & 0xFF0000u, b2 = b & 0xFF0000u, a3 = a & 0xFF000000u, b3 = b & 0xFF000000u;
+  return (a0 > b0 ? a0 : b0) | (a1 < b1 ? a1 : b1) | (a2 > b2 ? a2 : b2) | (a3 < b3 ? a3 : b3);
+}
+// The pair table of a range table: entry b of a row is the range over blocks
+// b and b + 1 of that row, which is what a term of the refinement reads (the
+// last block of the row stands alone).  Word w of a row from the table's words
+// w and w + 1 (last: w is the row's last word, there is no w + 1).
+LM_TB_HD inline uint32_t lm_tbr_pair_word(uint32_t w, uint32_t wnext, bool last) {
+  return lm_tb_range_merge(w, (w >> 16) | (last ? w & 0xFFFF0000u : wnext << 16));
+}
+// The range a term reads at block ba of a detector whose window ends before
+// block bendl (the second block is clipped to bendl - 1: at ba == bendl - 1
+// the term sees block ba alone, whatever the table holds beyond it).  plain,
+// pair: the row's entries of the range table and of its pair table; pair
+// null: the pair is formed from plain.
+LM_TB_HD inline void lm_tbr_pair_range(const uint16_t* pair, const uint16_t* plain, int ba, int bendl, unsigned& M,
+                                       unsigned& m) {
+  if (pair != nullptr) {
+    const unsigned q = ba == bendl - 1 ? plain[ba] : pair[ba];
+    M = q & 0xFFu;
+    m = q >> 8;
+  } else {
+    const unsigned qa = plain[ba], qb = plain[ba + 1 < bendl ? ba + 1 : bendl - 1];
+    M = (qa & 0xFFu) > (qb & 0xFFu) ? qa & 0xFFu : qb & 0xFFu;
+    m = (qa >> 8) < (qb >> 8) ? qa >> 8 : qb >> 8;
+  }
+}
+// The same for the LM_TBR_GC terms of a chunk at once, as k_tile_bound reads
+// them: w0 .. w2 are the pair table's words ba / 2 .. ba / 2 + 2 of the row
+// (ba: the block of the chunk's first term; they cover the entries ba .. ba +
+// 3 at either parity, and the words past a row's last block are never used),
+// x0 / x1 receive entries ba, ba + 1 / ba + 2, ba + 3.  lm_tbr_quad_get:
+// term j of the chunk; clip: this term stands at block bendl - 1, `alone` is
+// the plain table's entry there.
+LM_TB_HD inline void lm_tbr_quad_align(uint32_t w0, uint32_t w1, uint32_t w2, int ba, uint32_t& x0, uint32_t& x1) {
+  const int s = 16 * (ba & 1);
+  x0 = (uint32_t)(((uint64_t)w1 << 32 | w0) >> s);
+  x1 = (uint32_t)(((uint64_t)w2 << 32 | w1) >> s);
+}
+LM_TB_HD inline void lm_tbr_quad_get(uint32_t x0, uint32_t x1, int j, bool clip, unsigned alone, unsigned& M,
+                                     unsigned& m) {
+  const unsigned q = clip ? alone : ((j & 2 ? x1 : x0) >> (16 * (j & 1))) & 0xFFFFu;
+  M = q & 0xFFu;
+  m = q >> 8;
+}
+
 // The tile rule's second half for tile (ty, tx): every block proven at block
 // height rh (1 or LM_TB_H).
 LM_TB_HD inline bool lm_tbr_tile_skip(const uint8_t* bmax, const uint8_t* bmin, int nbw, int in_y, int in_x, int oh,
