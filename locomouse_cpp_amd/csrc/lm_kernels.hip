@@ -687,6 +687,9 @@ static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the d
 #ifndef LM_TBW_CR
 #define LM_TBW_CR 2  // k_tile_bound: entries a thread holds while the refined entries close up
 #endif
+#ifndef LM_TBW_ROW_LOOP
+#define LM_TBW_ROW_LOOP 1  // 1 = k_tile_bound<true> (lm_tbr_sum_rows_n) where all refined detectors allow it; 0 = lm_tbr_sum for all
+#endif
 __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
     const LmConst* __restrict__ Kp, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes, int s0,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
@@ -855,7 +858,9 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
 //      block) items of all three detectors, in wave-sized chunks of one
 //      detector each, the terms read from the pair table that the four-row
 //      windows are turned into after step 3 (3b: entry b is the range over
-//      blocks b and b + 1, which is what a term reads; see there);
+//      blocks b and b + 1, which is what a term reads; see there), by a loop
+//      without chunk stepping where the detectors' weight rows are one chunk
+//      of constants each (at most four tap groups: all of C3's; ROWS below);
 //      one compaction then drops the entries of proven tiles from all three
 //      segments.
 //   5. One global atomic per (workgroup, detector) on the slot group's segment
@@ -877,6 +882,14 @@ DEV int wave_append(bool p, int* ctr) {
 #ifndef LM_TBW_WPE
 #define LM_TBW_WPE 8  // amdgpu_waves_per_eu minimum: <= 64 VGPRs, eight workgroups per compute unit
 #endif
+// ROWS: step 4b sums the detectors of one chunk of constants per weight row
+// with lm_tbr_sum_rows_n (the others, and every detector of ROWS false, with
+// lm_tbr_sum).  The host launches ROWS true only where a refined detector is
+// such a one (lm_ctx::tbw_row_loop: all of C3's); elsewhere (C5) the kernel
+// holds the generic loop alone, instruction for instruction as it was compiled
+// before the row loops existed (with them next to it C5 lost 1.2 %; DESIGN.md
+// section 12).
+template <bool ROWS>
 __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(LM_TBW_WPE, 8))) void k_tile_bound(
     const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
@@ -1131,6 +1144,10 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   // at LM_TB_RH 1 (or over the rows of a short last tile row), the pairs formed
   // from B.  A tile with a block that stays unproven is marked and keeps its
   // entry, the others get flag 0 and the entries of each detector close up.
+  // With ROWS a detector of one chunk per row takes lm_tbr_sum_rows_n, the same
+  // terms in the same order with the group count a constant: no chunk counter,
+  // no guard per term, a fixed step of nw words to the next row's entries, and
+  // the select of the alone entry only at the row's last term.
   uint32_t* mark = work;  // (the work list is done with; one word per entry, the detectors' one after the other)
   int nr3[3], ent3[3];
 #pragma unroll
@@ -1172,7 +1189,10 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       const int nr = min(LM_TB_H, ohk - LM_TB_H * tyb);
       const int row0 = yb + LM_TB_H * tyb, ba0 = bl0 + xb;
       // the tile's four rows at once from the pair table of their windows
-      auto level_v = [&]() {
+      // (rows > 0: a detector of one chunk per row and `rows` tap groups, lm_tbr_sum_rows_n -- a row's words and
+      // alone entry lie a fixed nw words and one entry behind the row's before it, and the row's last term is the
+      // detector's last group; rows 0: any detector, lm_tbr_sum)
+      auto level_v = [&](auto rows) {
         const uint32_t* pw = V + row0 * nw + (ba0 >> 1);
         const uint16_t* alone = AL + k * als + row0;  // the windows' last block of the detector's window, alone:
         const bool clipped = ba0 + ng == bendl;       // what the last group reads when it stands there
@@ -1187,6 +1207,19 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
           qn = *alone;
         };
         fetch();
+        if constexpr (decltype(rows)::value > 0) {
+          constexpr int NG = decltype(rows)::value;  // (== ng: the row's last term is known where it is read)
+          return lm_tbr_sum_rows_n<NG>(kh, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
+                   if (g == 0) {  // the row's entries, and the next row's words on their way
+                     lm_tbr_quad_align(w0, w1, w2, ba0, x0, x1);
+                     q = qn;
+                     pw += nw;
+                     alone += 1;
+                     fetch();
+                   }
+                   lm_tbr_quad_get(x0, x1, g, g == NG - 1 && clipped, q, M, m);
+                 }) < 0.0;
+        }
         return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
           if (g % LM_TBR_GC == 0) {  // a chunk's first term: its entries, and the next chunk's words on their way
             const int c = g / LM_TBR_GC;
@@ -1215,7 +1248,19 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
           }
         });
       };
-      bool proven = nr == LM_TB_H && level_v();
+      using std::integral_constant;
+      bool proven;
+      if constexpr (!ROWS) {
+        proven = nr == LM_TB_H && level_v(integral_constant<int, 0>{});
+      } else {  // (nc and ng are uniform: a wave takes one of the loops)
+        proven = false;
+        if (nr != LM_TB_H) {
+        } else if (nc != 1) proven = level_v(integral_constant<int, 0>{});
+        else if (ng == 4) proven = level_v(integral_constant<int, 4>{});
+        else if (ng == 3) proven = level_v(integral_constant<int, 3>{});
+        else if (ng == 2) proven = level_v(integral_constant<int, 2>{});
+        else proven = level_v(integral_constant<int, 1>{});
+      }
       if (!proven && !(LM_TB_RH == LM_TB_H && nr == LM_TB_H)) {
         if (LM_TB_RH == LM_TB_H) {
           proven = level_b(0, nr);

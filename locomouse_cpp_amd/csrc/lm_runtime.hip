@@ -230,6 +230,12 @@ struct lm_ctx {
   // LM_TILE_REFINE=0: the tile bound alone decides (no refinement per output
   // block and tap group), in both kernels
   bool tb_refine = true;
+  // a detector that k_tile_bound refines has one chunk of group constants per
+  // weight row (lm_tbr_chunks == 1): the pre-pass is k_tile_bound<true>, whose
+  // refinement sums such a detector's rows without chunk stepping (and the
+  // others' with the generic loop); none has: k_tile_bound<false>, the generic
+  // loop alone
+  bool tbw_row_loop = false;
   DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off), then its P[i][g], N[i][g] (tbr_off)
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
@@ -878,6 +884,10 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
       K.tbw_lds[v] = (int32_t)lds;
       c->tbw_lds = std::max(c->tbw_lds, (size_t)lds);
     }
+    bool one_chunk = false;
+    for (int d = 0; d < LM_NDET; ++d)
+      one_chunk = one_chunk || (K.tbw_use[d] && K.tbr_on[d] && lm_tbr_chunks(K.tbr_ng[d]) == 1);
+    c->tbw_row_loop = LM_TBW_ROW_LOOP && one_chunk;
   }
   // LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
   // scaled by 2^s so that the largest |w| lands in [2^14, 2^15) (the rounding
@@ -944,7 +954,8 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   c->fstride = (nv + 255) / 256 * 256;
   HIPCHK(hipFuncSetAttribute((const void*)k_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tail_lds));
   HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound_ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tb_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
   for (const auto& P : c->corr_plan)
     for (size_t g = 0; g < P.groups.size(); ++g)
       HIPCHK(hipFuncSetAttribute(P.groups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds[g]));
@@ -1360,9 +1371,10 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
             dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.flags, dk.tail_flags, dk.tail_cnt, dk.tail_list,
             dk.pt_flags, dk.pt_cnt, dk.pt_list);
       else
-        k_tile_bound<<<dim3((unsigned)nproc, (unsigned)(K.tbw_nband[0] + K.tbw_nband[1])), LM_TB_THREADS, c->tbw_lds,
-                       st>>>(dK, L.rng.p, c->ext_slot_bytes / LM_INGEST_VEC, s_proc0, nproc, c->tb_const.p, dk.flags,
-                             dk.tail_flags, dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list);
+        (c->tbw_row_loop ? k_tile_bound<true> : k_tile_bound<false>)
+            <<<dim3((unsigned)nproc, (unsigned)(K.tbw_nband[0] + K.tbw_nband[1])), LM_TB_THREADS, c->tbw_lds, st>>>(
+                dK, L.rng.p, c->ext_slot_bytes / LM_INGEST_VEC, s_proc0, nproc, c->tb_const.p, dk.flags, dk.tail_flags,
+                dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list);
       T.end();
     }
   }

@@ -3,7 +3,8 @@
  * output tile, from per-row pixel ranges (plain C++: the host runtime, the
  * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
  * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp,
- * tests/cpp/tile_refine_check.cpp and tests/cpp/tile_pair_check.cpp share it),
+ * tests/cpp/tile_refine_check.cpp, tests/cpp/tile_pair_check.cpp and
+ * tests/cpp/tile_sum_rows_check.cpp share it),
  * and its refinement per 8-column output block and tap group (below,
  * lm_tbr_*).  Written for the tail detectors (hence the name); it serves the
  * point detectors too.
@@ -272,12 +273,13 @@ LM_TB_HD inline void lm_tbr_prepare(const float* w, int kh, int kw, int wstride,
       q[LM_TBR_GC] = n * (1.0 - 1e-12);  // rounded down (it is subtracted)
     }
 }
-// The one definition of a block's sum: rng(i, g, M, m) yields the largest and
-// smallest byte of weight row i's group g (unsigned references).  Every user
-// (the host, k_tile_bound_ref, k_tile_bound) goes through it, so equal ranges
-// give the same bit.
+// The one definition of a block's sum U: rng(i, g, M, m) yields the largest
+// and smallest byte of weight row i's group g (unsigned references).  Every
+// user (the host, k_tile_bound_ref, k_tile_bound) goes through it or through
+// lm_tbr_sum_rows (below: the same terms in the same order for detectors of
+// one chunk per row), so equal ranges give the same bit.
 template <class F>
-LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double bias, F&& rng) {
+LM_TB_HD inline double lm_tbr_sum(int kh, int ng, const double* C, double bias, F&& rng) {
   static_assert(LM_TBR_GC == 4, "a chunk is read as four P and four N");
   const int nc = lm_tbr_chunks(ng);
   double U = bias;
@@ -324,7 +326,72 @@ LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double
       if (++c == nc) c = 0, ++i;
     }
   }
-  return U < 0.0;
+  return U;
+}
+// lm_tbr_sum for a detector of one chunk per row (lm_tbr_chunks(ng) == 1: at
+// most LM_TBR_GC tap groups, which is every detector up to 25 taps wide and
+// the wider ones at a small in_x % 8): row i's constants are the eight doubles
+// at C + 8 i, so there is no chunk to count and none to pair; the rows are
+// taken two at a time only so that a row's constants are fetched, one row
+// ahead, into the registers of the row before it.  The terms, their order and
+// their guards (nt = ng) are lm_tbr_sum's: U is the same double bit for bit
+// (tests/cpp/tile_sum_rows_check.cpp).  lm_tbr_sum_rows_n: the group count NG
+// as a constant, so that a term's guard costs nothing and rng sees which term
+// is the row's last (g == NG - 1); lm_tbr_sum_rows chooses among them, and
+// takes lm_tbr_sum for any other group count.
+template <int NG, class F>
+LM_TB_HD inline double lm_tbr_sum_rows_n(int kh, const double* C, double bias, F&& rng) {
+  static_assert(LM_TBR_GC == 4 && NG >= 1 && NG <= LM_TBR_GC, "a row is read as four P and four N");
+  double U = bias;
+  auto row = [&](int i, double p0, double p1, double p2, double p3, double n0, double n1, double n2, double n3,
+                 auto&& ahead) {
+    unsigned M, m;
+    rng(i, 0, M, m);
+    ahead();
+    U += p0 * (double)M - n0 * (double)m;
+    if (NG > 1) {
+      rng(i, 1, M, m);
+      U += p1 * (double)M - n1 * (double)m;
+    }
+    if (NG > 2) {
+      rng(i, 2, M, m);
+      U += p2 * (double)M - n2 * (double)m;
+    }
+    if (NG > 3) {
+      rng(i, 3, M, m);
+      U += p3 * (double)M - n3 * (double)m;
+    }
+  };
+  if (kh <= 0) return U;
+  const double* q = C;
+  double a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5], a6 = q[6], a7 = q[7];
+  double b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0, b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+  for (int i = 0; i < kh; i += 2, q += 4 * LM_TBR_GC) {
+    // (past the last row the last row's constants once more: a fetch without a branch)
+    const double* qb = q + (i + 1 < kh ? 2 * LM_TBR_GC : 0);
+    row(i, a0, a1, a2, a3, a4, a5, a6, a7,
+        [&] { b0 = qb[0], b1 = qb[1], b2 = qb[2], b3 = qb[3], b4 = qb[4], b5 = qb[5], b6 = qb[6], b7 = qb[7]; });
+    if (i + 1 < kh) {
+      const double* qa = qb + (i + 2 < kh ? 2 * LM_TBR_GC : 0);
+      row(i + 1, b0, b1, b2, b3, b4, b5, b6, b7,
+          [&] { a0 = qa[0], a1 = qa[1], a2 = qa[2], a3 = qa[3], a4 = qa[4], a5 = qa[5], a6 = qa[6], a7 = qa[7]; });
+    }
+  }
+  return U;
+}
+template <class F>
+LM_TB_HD inline double lm_tbr_sum_rows(int kh, int ng, const double* C, double bias, F&& rng) {
+  switch (ng) {
+    case 1: return lm_tbr_sum_rows_n<1>(kh, C, bias, rng);
+    case 2: return lm_tbr_sum_rows_n<2>(kh, C, bias, rng);
+    case 3: return lm_tbr_sum_rows_n<3>(kh, C, bias, rng);
+    case 4: return lm_tbr_sum_rows_n<4>(kh, C, bias, rng);
+    default: return lm_tbr_sum(kh, ng, C, bias, rng);  // (more than one chunk per row, or no group: the generic form)
+  }
+}
+template <class F>
+LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double bias, F&& rng) {
+  return lm_tbr_sum(kh, ng, C, bias, rng) < 0.0;
 }
 // First block (of the view's) that output block xb reads at group 0, and the
 // end of the blocks the window touches (nbw: blocks per view row).
