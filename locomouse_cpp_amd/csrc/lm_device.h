@@ -12,6 +12,14 @@
 
 #include <stdint.h>
 
+// the small functions below serve kernels and the host; a plain C++ compiler
+// (tests/cpp, lm_tile_plan.h's users) sees them as ordinary inline functions
+#if defined(__HIPCC__)
+#define LM_HD __host__ __device__
+#else
+#define LM_HD
+#endif
+
 // Correlation tile width (k_corr_rw: 80 x 16 per wave; k_corr_gen: 80 x 48
 // per 192-thread workgroup, 16 x 12 threads of LM_C x 4 outputs).
 #define LM_C 5
@@ -46,7 +54,7 @@ static_assert((LM_FW == 40 || LM_FW == 80) && (LM_FH == 4 || LM_FH == 8), "dark-
 #define LM_TL_NC 64
 // first slot group of list segment c (G slot groups): the segment holds the
 // tiles of slot groups y0(c) .. y0(c + 1) - 1
-__host__ __device__ inline int lm_tl_y0(int c, int G) { return (c * G + LM_TL_NC - 1) / LM_TL_NC; }
+LM_HD inline int lm_tl_y0(int c, int G) { return (c * G + LM_TL_NC - 1) / LM_TL_NC; }
 
 // k_minmax: each frame split over LM_MM_SPLIT workgroups of LM_MM_THREADS
 #define LM_MM_SPLIT 8
@@ -130,26 +138,19 @@ struct LmConst {
   // the bound per detector d: tb_skip[d]: it may prove tiles (else every tile,
   // of a point detector every bright tile, is listed); its P_i at tb_off[d],
   // N_i at tb_off[d] + kh of the bound constants; tb_rng[d]: byte offset of
-  // the detector's row ranges in k_tile_bound's LDS (after the view's block
-  // ranges); tb_lds[v]: the kernel's LDS bytes for view v
+  // the detector's row ranges in k_tile_bound_ref's LDS (after the view's
+  // block ranges); tb_lds[v]: that kernel's LDS bytes for view v.  These and
+  // the tbw_* / tbr_* below are filled by lm_tile_plan.h.
   int32_t tb_skip[LM_NDET], tb_off[LM_NDET], tb_rng[LM_NDET], tb_lds[2];
   double tb_bias[LM_NDET];
-  // k_tile_bound (the banded kernel that reads k_ingest's block ranges; the
-  // tb_rng / tb_lds above are k_tile_bound_ref's).  View v is split into
-  // tbw_nband[v] bands of tbw_br[v] tile rows of each of its detectors' grids.
-  // tbw_use[d]: detector d's bound is used (tb_skip[d], and its band tables
-  // fit the LDS); tbw_inv[d]: lm_rcp of its tile columns.  The band's LDS:
-  // block ranges (u16 max | min << 8 per ext row and block of the columns
-  // tbw_blo[v] .. + tbw_nbk[v], both even; at most tbw_rows[v] rows) at 0,
-  // their four-row windows at tbw_v[v] (which become their pair table in
-  // place -- entry b: the range over blocks b and b + 1, lm_tail_bound.h --
-  // when a detector of the view is refined; then the windows' entries at the
-  // last block of each detector's window, tbw_rows[v] per detector, at
-  // tbw_al[v]); per detector P_i and N_i at
-  // tbw_pn[d], the window table (lm_tail_bound.h: wmax, then wmin at +
-  // tbw_wsz[d]) at tbw_win[d], the list entries of the band at tbw_ent[d];
-  // the tiles to evaluate at tbw_work[v].  All byte offsets; tbw_lds[v] bytes
-  // in all.
+  // k_tile_bound (the banded kernel that reads k_ingest's block ranges).  View
+  // v is split into tbw_nband[v] bands of tbw_br[v] tile rows of each of its
+  // detectors' grids.  tbw_use[d]: detector d's bound is used (tb_skip[d], and
+  // its band tables fit the LDS); tbw_inv[d]: lm_rcp of its tile columns.  The
+  // rest are the byte offsets and sizes of the band's LDS regions, tbw_lds[v]
+  // bytes in all: lm_tile_plan.h defines the layout (at its top, and
+  // lm_tbw_layout), and tests/cpp/tile_plan_check.cpp checks it against what
+  // the kernel reads.
   int32_t tbw_br[2], tbw_nband[2], tbw_blo[2], tbw_nbk[2], tbw_rows[2], tbw_v[2], tbw_al[2], tbw_work[2], tbw_lds[2];
   int32_t tbw_use[LM_NDET], tbw_pn[LM_NDET], tbw_win[LM_NDET], tbw_wsz[LM_NDET], tbw_ent[LM_NDET];
   uint32_t tbw_inv[LM_NDET];
@@ -192,13 +193,13 @@ struct LmConst {
 // x / d without a division, for x >= 0 and x d < 2^31: lm_div(x, lm_rcp(d))
 // (lm_rcp(d) = floor(2^31 / d) + 1 = (2^31 + e) / d with 0 < e <= d, so the
 // product exceeds x / d by x e / (d 2^31) < 1 / d)
-__host__ __device__ inline uint32_t lm_rcp(int d) { return (uint32_t)(0x80000000u / (uint32_t)d + 1u); }
-__host__ __device__ inline int lm_div(int x, uint32_t rcp) { return (int)(((uint64_t)(uint32_t)x * rcp) >> 31); }
+LM_HD inline uint32_t lm_rcp(int d) { return (uint32_t)(0x80000000u / (uint32_t)d + 1u); }
+LM_HD inline int lm_div(int x, uint32_t rcp) { return (int)(((uint64_t)(uint32_t)x * rcp) >> 31); }
 
 // k_tile_bound's band j of br tile rows, for a detector with ty tile rows:
 // its first tile row *t0, its tile rows *nty (0: the detector ends above the
 // band) and the output rows inside them (returned)
-__host__ __device__ inline int lm_tbw_band(const LmDet& D, int ty, int br, int j, int* t0, int* nty) {
+LM_HD inline int lm_tbw_band(const LmDet& D, int ty, int br, int j, int* t0, int* nty) {
   *t0 = j * br;
   const int t1 = ty < *t0 + br ? ty : *t0 + br;
   *nty = t1 > *t0 ? t1 - *t0 : 0;
@@ -283,10 +284,7 @@ struct LmPackLayout {  // byte offsets inside the packed buffer
   int64_t cand, p22d, side_y, side_s, unary, jc, ir, pr, bytes;
 };
 
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline LmPackLayout lm_pack_layout(int n, const int64_t* tot) {
+LM_HD inline LmPackLayout lm_pack_layout(int n, const int64_t* tot) {
   LmPackLayout L;
   int64_t o = 0;
   auto take = [&o](int64_t bytes) {

@@ -35,6 +35,7 @@
 
 #include "lm_dev_common.h"
 #include "lm_tail_bound.h"
+#include "lm_tile_plan.h"
 
 // ------------------------------------------------------------------ helpers
 
@@ -193,9 +194,7 @@ DEV uint8_t ipad_pixel_t(FP __restrict__ F, const uint8_t* __restrict__ bkg, con
 // LUTs and the store remain.  Where the 16 source pixels are consecutive in
 // the frame (a calibration map that is locally a translation, flipped or not)
 // the gather is five aligned dword loads instead of sixteen byte loads.
-#define LM_INGEST_VEC 16
-static_assert(LM_FW >= LM_INGEST_VEC, "a 16-byte chunk spans at most two flag tiles");
-#define LM_INGEST_MAXTX 128  // flag-grid columns a band's workgroup can hold (ow <= 128 LM_FW)
+// (LM_INGEST_VEC, LM_INGEST_MAXTX: lm_tile_plan.h)
 
 // Gather index of crop pixel I_PAD (R, C) (-1 outside I_UNPAD).
 DEV int ingest_index(const LmConst& K, const int32_t* __restrict__ cal, int R, int C) {
@@ -299,8 +298,8 @@ DEV uint32_t bright_bytes(uint32_t w) {
 DEV uint32_t byte_mask4(uint32_t n) { return ((n * 0x00204081u) & 0x01010101u) << 7; }
 
 // Largest byte | smallest byte << 8 of the eight bytes of a, b: the pixel range
-// of an aligned block of LM_TB_BLK columns (lm_tail_bound.h).
-static_assert(LM_TB_BLK == 8 && LM_INGEST_VEC == 2 * LM_TB_BLK, "a 16-byte chunk holds two blocks");
+// of an aligned block of LM_TB_BLK columns (lm_tail_bound.h; a 16-byte chunk
+// holds two of them: lm_tile_plan.h).
 DEV uint32_t block_range(uint32_t a, uint32_t b) {
   uint32_t mx = 0u, mn = 255u;
 #pragma unroll
@@ -673,11 +672,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
 // k_tile_bound_ref is the first form of the pre-pass (LM_TILE_BOUND_REF=1):
 // it reads the crops themselves and reduces a whole view per workgroup.  It is
 // kept as the reference that k_tile_bound (below) is tested against.
-static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the dark-tile grid's");
-#define LM_TB_THREADS 256
-#ifndef LM_TBW_TILES
-#define LM_TBW_TILES LM_TB_THREADS  // k_tile_bound: about this many tiles of a view's detectors per band
-#endif
+// (LM_TB_THREADS, LM_TBW_TILES, LM_TBW_ROW_LOOP: lm_tile_plan.h, which plans both kernels' LDS)
 #ifndef LM_TBW_LD
 #define LM_TBW_LD 8  // k_tile_bound: a thread's loads of block ranges in flight
 #endif
@@ -686,9 +681,6 @@ static_assert(LM_TB_W == LM_FW && LM_TB_H == LM_FH, "the bound's tiles are the d
 #endif
 #ifndef LM_TBW_CR
 #define LM_TBW_CR 2  // k_tile_bound: entries a thread holds while the refined entries close up
-#endif
-#ifndef LM_TBW_ROW_LOOP
-#define LM_TBW_ROW_LOOP 1  // 1 = k_tile_bound<true> (lm_tbr_sum_rows_n) where all refined detectors allow it; 0 = lm_tbr_sum for all
 #endif
 __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
     const LmConst* __restrict__ Kp, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes, int s0,
@@ -889,6 +881,9 @@ DEV int wave_append(bool p, int* ctr) {
 // holds the generic loop alone, instruction for instruction as it was compiled
 // before the row loops existed (with them next to it C5 lost 1.2 %; DESIGN.md
 // section 12).
+// TBW_SEL: detector k's member of one of the kernel's per-detector arrays,
+// chosen among the three uniform values, not loaded per lane.
+#define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
 template <bool ROWS>
 __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(LM_TBW_WPE, 8))) void k_tile_bound(
     const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
@@ -1106,8 +1101,6 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const bool act = w0 + tid < nwork;
     const uint32_t item = act ? work[w0 + tid] : 0u;
     const int k = (int)(item >> 28), j = (int)(item & 0x0FFFFFFFu);
-    // (the detector's constants chosen among the three uniform sets, not loaded per lane)
-#define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
     const int tb = TBW_SEL(tbase);
     bool keep = act;
     if (act && TBW_SEL(use)) {
@@ -1120,7 +1113,6 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     }
     // (a tile that goes on to the refinement gets its flag there)
     if (act && !(keep && TBW_SEL(refine))) TBW_SEL(fl)[tb + j] = keep ? 1 : 0;
-#undef TBW_SEL
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {
       const bool mine = act && keep && k == kk;
@@ -1156,7 +1148,6 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     ent3[k] = K.tbw_ent[3 * v + k];
   }
   const int nref = nr3[0] + nr3[1] + nr3[2];
-#define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
   if (nref > 0) {
     for (int t = tid; t < nref; t += T) mark[t] = 0u;
     __syncthreads();
@@ -1307,7 +1298,6 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       if (TBW_SEL(nr3) > 0) s_n[k] = s_m[k];
     }
   }
-#undef TBW_SEL
   __syncthreads();
   // 5. this workgroup's list segments and their counters, as in k_ingest
   const int G = (nslot + LM_INGEST_FB - 1) / LM_INGEST_FB;
@@ -1331,6 +1321,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     for (int p = tid; p < s_n[k]; p += T) out[p] = ent[p];
   }
 }
+#undef TBW_SEL
 
 #include "lm_corr.h"  // the correlation kernels are their own translation unit (lm_corr.hip)
 

@@ -222,14 +222,16 @@ struct lm_ctx {
   // the same for the point detectors' bright tiles (LM_CORR_POINTSKIP=0:
   // compute every bright tile; never in the f16 mode or with LM_CORR_DARK=0)
   bool pointskip_on = true;
-  size_t tb_lds = 0;        // k_tile_bound_ref's LDS bytes (the larger view's)
-  size_t tbw_lds = 0;       // k_tile_bound's (the larger view's band)
+  // The tile-bound pre-pass (planned by lm_tile_plan.h; the two skips above
+  // hold its answer after every force-off):
   // LM_TILE_BOUND_REF=1: the pre-pass is k_tile_bound_ref (it reads the crops;
   // k_ingest then writes no block ranges)
   bool tb_ref = false;
   // LM_TILE_REFINE=0: the tile bound alone decides (no refinement per output
   // block and tap group), in both kernels
   bool tb_refine = true;
+  size_t tb_lds = 0;        // k_tile_bound_ref's LDS bytes (the larger view's)
+  size_t tbw_lds = 0;       // k_tile_bound's (the larger view's band)
   // a detector that k_tile_bound refines has one chunk of group constants per
   // weight row (lm_tbr_chunks == 1): the pre-pass is k_tile_bound<true>, whose
   // refinement sums such a detector's rows without chunk stepping (and the
@@ -293,7 +295,23 @@ struct lm_ctx {
 
 namespace {
 
-void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const lm_model* M) {
+// ------------------------------------------------------------------------
+// The steps of validate_and_build (below), in its order.  Each states what it
+// reads and what it fills; only upload_constants touches HIP.
+
+// The model's detectors in DET_* order.
+struct ModelDets {
+  const lm_detector* p[LM_NDET];
+  const lm_detector* operator[](int d) const { return p[d]; }
+};
+ModelDets model_dets(const lm_model* M) {
+  return {{&M->paw_bottom, &M->snout_bottom, &M->tail_bottom, &M->paw_side, &M->snout_side, &M->tail_side}};
+}
+
+// Checks the parameters, the setup and the model (the message texts are the
+// reference's or name its line: tests and the reference mapping depend on
+// them).  Reads su, P, M; fills nothing.
+void check_inputs(const lm_setup* su, const lm_params* P, const lm_model* M) {
   if (!su || !P || !M) throw std::invalid_argument("null setup/params/model");
   // LocoMouse_Parameters (:33-249)
   if (P->conn_comp_connectivity != 4 && P->conn_comp_connectivity != 8)
@@ -353,7 +371,7 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   if (ub.width <= 0 || ub.height <= 0 || us.width <= 0 || us.height <= 0)
     throw std::runtime_error("Empty mouse bounding box: cropBoundingBox / filter2D would work on an empty image.");
   // model (:3095-3162)
-  const lm_detector* dets[6] = {&M->paw_bottom, &M->snout_bottom, &M->tail_bottom, &M->paw_side, &M->snout_side, &M->tail_side};
+  const ModelDets dets = model_dets(M);
   const char* names[6] = {"modelPaw_bottom", "modelSnout_bottom", "modelTail_bottom", "modelPaw_side", "modelSnout_side", "modelTail_side"};
   for (int d = 0; d < 6; ++d) {
     if (!dets[d]->weights || dets[d]->rows <= 0 || dets[d]->cols <= 0)
@@ -368,10 +386,37 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   }
   if (su->corr_precision != LM_CORR_FP32 && su->corr_precision != LM_CORR_F16)
     throw std::invalid_argument("corr_precision must be LM_CORR_FP32 or LM_CORR_F16.");
+}
 
-  c->setup = *su;
-  c->params = *P;
-  lm_geometry& g = c->geo;
+// The environment's switches, read at every context creation (LM_RW_WIDEN
+// alone is read once per process, in fill_detectors).  Fills the context's
+// kprof_on, dark_on, tb_refine, tb_ref and returns what the tile plan is asked
+// for; tailskip_on / pointskip_on are set from the plan's answer.
+LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
+  auto flag = [](const char* name, bool dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) != 0 : dflt;
+  };
+  c->kprof_on = flag("LM_KPROF", false);
+  c->dark_on = flag("LM_CORR_DARK", true);
+  c->tb_refine = flag("LM_TILE_REFINE", true);
+  c->tb_ref = flag("LM_TILE_BOUND_REF", false);
+  LmTileSwitches sw;
+  sw.tailskip = flag("LM_CORR_TAILSKIP", true);
+  sw.pointskip = flag("LM_CORR_POINTSKIP", true);
+  sw.refine = c->tb_refine;
+  sw.f16 = su->corr_precision == LM_CORR_F16;
+  sw.dark = c->dark_on;
+  return sw;
+}
+
+// The geometry of the boxes and the model's sizes (LocoMouse::LocoMouse
+// :307-345, initializeFeatureLoop :655-769, LocoMouse_Model :3095-3179).
+// Pure: reads su, P, M and returns the struct (every byte of it set).
+lm_geometry make_geometry(const lm_setup* su, const lm_params* P, const lm_model* M) {
+  const int NR = su->calib_rows, NC = su->calib_cols;
+  const lm_rect ub = P->bounding_box_bottom, us = P->bounding_box_side;
+  lm_geometry g;
   std::memset(&g, 0, sizeof(g));
   g.n_rows = NR;
   g.n_cols = NC;
@@ -422,15 +467,18 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   g.match_box_snout_side = mrect(M->snout_side);
   if (g.ong_nx <= 0 || g.ong_ny <= 0) throw std::invalid_argument("occlusion grid is empty for this bounding box.");
   if (tw <= 0) throw std::invalid_argument("tail box width is 0.");
+  return g;
+}
 
-  c->bb_x = ub.x + ub.width;  // getBoundingBox provided-box branch (:547-557)
-  c->bb_ys = us.y + us.height;
-  c->bb_yb = ub.y + ub.height;
-  c->npix = (int)nv;
-
-  // ---------------- kernel constants
-  LmConst& K = c->K;
-  std::memset(&K, 0, sizeof(K));
+// The six detectors, their correlation tiles and each view's extended crop
+// (every pixel a tap of one of its detectors reads), including LM_RW_WIDEN.
+// Reads g, su, M; fills K.det[] (but chunk_rows and the f16 fields: the
+// correlation plans and f16_fragments), n_tiles and ext_*.  Returns the floats
+// of the padded weights.
+int fill_detectors(LmConst& K, const lm_geometry& g, const lm_setup* su, const lm_model* M) {
+  const ModelDets dets = model_dets(M);
+  const lm_rect ub = g.bb_bottom_mouse, us = g.bb_side_mouse;  // (the provided boxes' sizes)
+  const int tw = g.tail_box_width;
   const int view_of[6] = {0, 0, 0, 1, 1, 1};
   const int kind_of[6] = {0, 0, 1, 0, 0, 1};
   const int list_of[6] = {LIST_PAW_B, LIST_SNOUT_B, 0, LIST_PAW_S, LIST_SNOUT_S, 1};
@@ -515,6 +563,12 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
     D.m_y -= K.ext_oy[D.view];
     D.m_x -= K.ext_ox[D.view];
   }
+  return w_off;
+}
+
+// Image constants.  Reads g, su, P; fills crop_*, unpad_*, the video and
+// image sizes, the padding, flip, tail_w / tail_hb / tail_hs, connectivity.
+void fill_image_constants(LmConst& K, const lm_geometry& g, const lm_setup* su, const lm_params* P) {
   K.crop_h[0] = g.bb_bottom_mouse_pad.height;
   K.crop_w[0] = g.bb_bottom_mouse_pad.width;
   K.crop_h[1] = g.bb_side_mouse_pad.height;
@@ -525,50 +579,60 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   K.unpad_x[1] = g.spre_t_w;
   K.video_rows = su->video_rows;
   K.video_cols = su->video_cols;
-  K.n_rows = NR;
-  K.n_cols = NC;
+  K.n_rows = g.n_rows;
+  K.n_cols = g.n_cols;
   K.pad_pre_rows = g.pad_pre_rows;
   K.pad_pre_cols = g.pad_pre_cols;
   K.ipad_rows = g.ipad_rows;
   K.ipad_cols = g.ipad_cols;
   K.flip = su->flip ? 1 : 0;
-  K.tail_w = tw;
-  K.tail_hb = ub.height;
-  K.tail_hs = us.height;
+  K.tail_w = g.tail_box_width;
+  K.tail_hb = g.bb_bottom_mouse.height;
+  K.tail_hs = g.bb_side_mouse.height;
   K.connectivity = P->conn_comp_connectivity;
-  // dark-tile flags of the point detectors' outputs (paw and snout of a view
-  // share the output region, out_rel above)
-  {
-    int o = 0;
-    for (int v = 0; v < 2; ++v) {
-      const LmDet& D = K.det[v ? DET_PAW_S : DET_PAW_B];
-      K.fl_tx[v] = (D.ow + LM_FW - 1) / LM_FW;
-      K.fl_ty[v] = (D.oh + LM_FH - 1) / LM_FH;
-      K.fl_off[v] = o;
-      o += (K.fl_tx[v] * K.fl_ty[v] + 3) / 4 * 4;
-    }
-    K.fl_slot = o;
-    K.tl_stride = c->nslots * std::max(K.fl_tx[0] * K.fl_ty[0], K.fl_tx[1] * K.fl_ty[1]);
-    if (K.fl_tx[0] * K.fl_ty[0] > 65535 || K.fl_tx[1] * K.fl_ty[1] > 65535 || c->nslots > 65535 ||
-        std::max(K.fl_tx[0], K.fl_tx[1]) > LM_INGEST_MAXTX)
-      throw std::invalid_argument("bounding box or batch too large for the correlation tile lists.");
-    // k_ingest's bands: 8 ext rows each, aligned with the flag grid's rows
-    int maxcw = 0;
-    for (int v = 0; v < 2; ++v) {
-      const LmDet& D = K.det[v ? DET_PAW_S : DET_PAW_B];
-      K.fl_my[v] = D.m_y;
-      K.fl_mx[v] = D.m_x;
-      K.fl_oh[v] = D.oh;
-      K.fl_ow[v] = D.ow;
-      const int above = (D.m_y + 7) / 8;  // bands above the output rows (m_y >= 0)
-      K.ing_b0[v] = -above;
-      K.ing_nb[v] = above + (K.ext_h[v] - D.m_y + 7) / 8;
-      maxcw = std::max(maxcw, K.ext_w[v] / LM_INGEST_VEC);
-    }
-    K.ing_threads = std::min(1024, (8 * maxcw + 63) / 64 * 64);
+}
+
+// The dark-tile flag grid of the point detectors' outputs (paw and snout of a
+// view share the output region) and k_ingest's bands.  Reads det[], ext_h,
+// ext_w, nslots; fills fl_*, tl_stride, ing_*.
+void fill_flag_grid(LmConst& K, int nslots) {
+  int o = 0;
+  for (int v = 0; v < 2; ++v) {
+    const LmDet& D = K.det[v ? DET_PAW_S : DET_PAW_B];
+    K.fl_tx[v] = (D.ow + LM_FW - 1) / LM_FW;
+    K.fl_ty[v] = (D.oh + LM_FH - 1) / LM_FH;
+    K.fl_off[v] = o;
+    o += (K.fl_tx[v] * K.fl_ty[v] + 3) / 4 * 4;
   }
-  // k_tail's LDS: bitmaps, column tables and moment tiles from the geometry,
-  // plus as many runs as fit 64 KiB (more go to global scratch)
+  K.fl_slot = o;
+  K.tl_stride = nslots * std::max(K.fl_tx[0] * K.fl_ty[0], K.fl_tx[1] * K.fl_ty[1]);
+  if (K.fl_tx[0] * K.fl_ty[0] > 65535 || K.fl_tx[1] * K.fl_ty[1] > 65535 || nslots > 65535 ||
+      std::max(K.fl_tx[0], K.fl_tx[1]) > LM_INGEST_MAXTX)
+    throw std::invalid_argument("bounding box or batch too large for the correlation tile lists.");
+  // k_ingest's bands: 8 ext rows each, aligned with the flag grid's rows
+  int maxcw = 0;
+  for (int v = 0; v < 2; ++v) {
+    const LmDet& D = K.det[v ? DET_PAW_S : DET_PAW_B];
+    K.fl_my[v] = D.m_y;
+    K.fl_mx[v] = D.m_x;
+    K.fl_oh[v] = D.oh;
+    K.fl_ow[v] = D.ow;
+    const int above = (D.m_y + 7) / 8;  // bands above the output rows (m_y >= 0)
+    K.ing_b0[v] = -above;
+    K.ing_nb[v] = above + (K.ext_h[v] - D.m_y + 7) / 8;
+    maxcw = std::max(maxcw, K.ext_w[v] / LM_INGEST_VEC);
+  }
+  K.ing_threads = std::min(1024, (8 * maxcw + 63) / 64 * 64);
+}
+
+// k_tail's LDS: bitmaps, column tables and moment tiles from the geometry,
+// plus as many runs as fit 64 KiB (more go to global scratch).  Reads g;
+// fills K.tail_ntc, K.tail_cap and the context's tail_lds, tail_big,
+// tail_ws_slot.
+void plan_tail_lds(lm_ctx* c, const lm_geometry& g) {
+  LmConst& K = c->K;
+  const lm_rect ub = g.bb_bottom_mouse, us = g.bb_side_mouse;
+  const int tw = g.tail_box_width;
   K.tail_ntc = (((tw - 1) / 15 + 1) + 31) / 32;
   K.tail_cap = 4096;
   while (K.tail_cap > 64 && tail_layout(tw, ub.height, us.height, K.tail_cap, K.tail_ntc).bytes > 64 * 1024) K.tail_cap -= 64;
@@ -581,6 +645,12 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
     c->tail_lds = 0;
     c->tail_ws_slot = ((int64_t)tail_layout(tw, ub.height, us.height, 0, K.tail_ntc).bytes + 255) / 256 * 256;
   }
+}
+
+// List and cost constants.  Reads g, P, M and det[].oh / ow; fills list_*,
+// keys_per_slot, the matching costs, the occlusion grid, bb_bottom_*, spre_*,
+// match_*, size_*, prior and the grey-level LUT.
+void fill_list_and_cost_constants(LmConst& K, const lm_geometry& g, const lm_params* P, const lm_model* M) {
   int64_t off = 0;
   for (int l = 0; l < LM_NLIST; ++l) {
     const int d = l == 0 ? DET_PAW_B : l == 1 ? DET_SNOUT_B : l == 2 ? DET_PAW_S : DET_SNOUT_S;
@@ -593,13 +663,13 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   K.alpha_vel_bottom = P->alpha_vel_bottom;
   K.pairwise_occluded_cost = P->pairwise_occluded_cost;
   K.max_displacement_bottom = P->max_displacement_bottom;
-  K.ong_spacing_bottom = sp;
+  K.ong_spacing_bottom = P->occlusion_grid_spacing_pixels_bottom;
   K.ong_nx = g.ong_nx;
   K.ong_ny = g.ong_ny;
   K.ong_br_x = g.ong_br_x;
   K.ong_br_y = g.ong_br_y;
-  K.bb_bottom_w = ub.width;
-  K.bb_bottom_h = ub.height;
+  K.bb_bottom_w = g.bb_bottom_mouse.width;
+  K.bb_bottom_h = g.bb_bottom_mouse.height;
   K.spre_b_w = g.spre_b_w;
   K.spre_b_h = g.spre_b_h;
   K.spre_t_w = g.spre_t_w;
@@ -629,8 +699,13 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   }
   K.gray_lut_on = P->transform_gray_values && !P->use_reference_image_brightness ? 1 : 0;
   for (int i = 0; i < 256; ++i) K.gray_lut[i] = K.gray_lut_on ? (uint8_t)P->gray_value_transformation[i] : (uint8_t)i;
+}
 
-  // per-slot sizes
+// Per-slot sizes of the lanes' buffers.  Reads K (ext_*, tail_*, det[],
+// list_cap, ong_*); fills K.tail_nw, K.tail_bm_words and the context's
+// ext_slot_bytes, tailbin_slot_bytes, dbg_off, dbg_slot_floats, gscratch_slot.
+void slot_sizes(lm_ctx* c) {
+  LmConst& K = c->K;
   c->ext_slot_bytes = ((int64_t)K.ext_h[0] * K.ext_w[0] + (int64_t)K.ext_h[1] * K.ext_w[1] + 255) / 256 * 256;
   K.tail_nw = 2 * ((K.tail_w + 63) / 64);
   K.tail_bm_words = (K.tail_hb + K.tail_hs) * K.tail_nw;
@@ -647,13 +722,17 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   // per entry; then reused by k_post for lists beyond its LDS capacity
   // (offsets np + Nong + 1, motion flags 2 np, counts 2 np: 32-bit each)
   c->gscratch_slot = std::max(3 * (int64_t)np, (5 * (int64_t)np + K.ong_nx * K.ong_ny + 2) / 2 + 1);
+}
+
+// The two correlation plans.  Detectors grouped by correlation kernel: one
+// width-specialised k_corr_rw launch per width, every other detector in one
+// k_corr_gen launch.  Each launch gets exactly the LDS its detectors' rings /
+// windows need, so narrow groups keep more waves per CU.  Reads det[] and the
+// setup's precision and filter arithmetic; fills c->unfused, c->corr_plan[]
+// and det[].chunk_rows.
+void build_corr_plans(lm_ctx* c, const lm_setup* su) {
+  LmConst& K = c->K;
   c->unfused = su->filter_arith == LM_FILTER_UNFUSED;
-  if (const char* v = getenv("LM_KPROF")) c->kprof_on = atoi(v) != 0;
-  if (const char* v = getenv("LM_CORR_DARK")) c->dark_on = atoi(v) != 0;
-  // Detectors grouped by correlation kernel: one width-specialised k_corr_rw
-  // launch per width, every other detector in one k_corr_gen launch.  Each
-  // launch gets exactly the LDS its detectors' rings / windows need, so narrow
-  // groups keep more waves per CU.
   // ring detectors ordered longest waves ((kh + 2) x kw taps) first
   int order[6] = {0, 1, 2, 3, 4, 5};
   std::stable_sort(order, order + 6, [&](int x, int y) {
@@ -705,194 +784,28 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
       P.lds[gi] = std::max(P.lds[gi], need);
     }
   }
+}
 
-  // weights (float, rows zero-padded to kwp) and TM imadjust LUT
+// The fp32 weights the kernels use: rows zero-padded to kwp, detector d's at
+// det[d].w_off; w_off floats in all (fill_detectors).  Reads det[], M.
+std::vector<float> pad_weights(const LmConst& K, const lm_model* M, int w_off) {
+  const ModelDets dets = model_dets(M);
   std::vector<float> wts((size_t)w_off, 0.f);
   for (int d = 0; d < 6; ++d) {
     const LmDet& D = K.det[d];
     for (int i = 0; i < D.kh; ++i)
       for (int j = 0; j < D.kw; ++j) wts[(size_t)D.w_off + i * D.kwp + j] = (float)dets[d]->weights[(size_t)i * D.kw + j];
   }
-  // tail tiles: the grid of LM_FW x LM_FH tiles per tail detector and the
-  // bound's constants (lm_tail_bound.h) from the fp32 weights the kernels use
-  std::vector<double> tbc;
-  if (const char* v = getenv("LM_CORR_TAILSKIP")) c->tailskip_on = atoi(v) != 0;
-  if (const char* v = getenv("LM_CORR_POINTSKIP")) c->pointskip_on = atoi(v) != 0;
-  if (su->corr_precision == LM_CORR_F16) c->tailskip_on = c->pointskip_on = false;  // the bound is for the fp32 chain
-  if (!c->dark_on) c->pointskip_on = false;  // it starts from k_ingest's bright flags
-  if (const char* v = getenv("LM_TILE_REFINE")) c->tb_refine = atoi(v) != 0;
-  {
-    int o = 0, mt = 0;
-    for (int t = 0; t < 2; ++t) {
-      const LmDet& D = K.det[t ? DET_TAIL_S : DET_TAIL_B];
-      K.tt_tx[t] = (D.ow + LM_FW - 1) / LM_FW;
-      K.tt_ty[t] = (D.oh + LM_FH - 1) / LM_FH;
-      K.tt_off[t] = o;
-      o += (K.tt_tx[t] * K.tt_ty[t] + 3) / 4 * 4;
-      mt = std::max(mt, K.tt_tx[t] * K.tt_ty[t]);
-    }
-    K.tt_slot = o;
-    K.tt_stride = c->nslots * mt;
-    // (list entries hold slot << 16 | tile)
-    if (mt > 65535 || c->nslots > 65535) c->tailskip_on = false;
-    // the point detectors' own flags: k_ingest's layout once per feature (lists: tl_stride each)
-    static_assert(LIST_PAW_B == 0 && LIST_SNOUT_B == 1 && LIST_PAW_S == 2 && LIST_SNOUT_S == 3, "list l: feature l & 1");
-    K.pt_plane = (int64_t)K.fl_slot * c->nslots;
-    if (K.fl_tx[0] * K.fl_ty[0] > 65535 || K.fl_tx[1] * K.fl_ty[1] > 65535 || c->nslots > 65535) c->pointskip_on = false;
-    // the bound's constants per detector and k_tile_bound's LDS per view: the
-    // view's block ranges, then the row ranges of each detector whose bound is
-    // usable and fits (the tail detector first)
-    constexpr int64_t kTileBoundLds = 144 * 1024;
-    constexpr int64_t kTileBoundWgLds = 64 * 1024;  // k_tile_bound's, per band
-    for (int v = 0; v < 2; ++v) {
-      int64_t lds = 2 * (int64_t)K.ext_h[v] * (K.ext_w[v] / LM_TB_BLK);
-      bool any = false;
-      for (int d : {3 * v + 2, 3 * v, 3 * v + 1}) {
-        const LmDet& D = K.det[d];
-        K.tb_off[d] = (int32_t)tbc.size();
-        tbc.resize(tbc.size() + 2 * (size_t)D.kh);
-        K.tb_skip[d] = lm_tb_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.delta, tbc.data() + K.tb_off[d],
-                                     tbc.data() + K.tb_off[d] + D.kh, &K.tb_bias[d]);
-        const int64_t rows = (int64_t)D.oh + D.kh - 1, wcols = (int64_t)D.ow + D.kw - 1;
-        const int64_t need = 2 * rows * (D.kind != 0 ? K.tt_tx[v] : K.fl_tx[v]);
-        const bool inside = D.in_y >= 0 && D.in_x >= 0 && D.in_y + rows <= K.ext_h[v] && D.in_x + wcols <= K.ext_w[v];
-        if (!(D.kind != 0 ? c->tailskip_on : c->pointskip_on) || !inside || lds + need > kTileBoundLds) K.tb_skip[d] = 0;
-        K.tb_rng[d] = K.tb_skip[d] ? (int32_t)lds : 0;
-        if (K.tb_skip[d]) {
-          lds += need;
-          any = true;
-        }
-        // the refinement's constants per tap group (off wherever the skip is)
-        K.tbr_on[d] = K.tb_skip[d] && c->tb_refine ? 1 : 0;
-        K.tbr_ng[d] = K.tbr_on[d] ? lm_tbr_groups(D.in_x, D.kw) : 0;
-        tbc.resize((tbc.size() + 7) / 8 * 8);  // (a chunk of group constants is 64 bytes, kept aligned)
-        K.tbr_off[d] = (int32_t)tbc.size();
-        if (K.tbr_on[d]) {
-          tbc.resize(tbc.size() + (size_t)lm_tbr_const_size(D.kh, K.tbr_ng[d]));
-          lm_tbr_prepare(wts.data() + D.w_off, D.kh, D.kw, D.kwp, D.in_x, tbc.data() + K.tbr_off[d]);
-        }
-      }
-      K.tb_lds[v] = any ? (int32_t)lds : 0;
-      c->tb_lds = std::max(c->tb_lds, (size_t)K.tb_lds[v]);
-    }
-    // k_tile_bound's bands (LmConst::tbw_*): tile rows per band so that the
-    // band's tiles over the view's detectors are about one workgroup's
-    // threads, evenly over the bands; the LDS of the largest band, with the
-    // same rule for what does not fit
-    if (const char* e = getenv("LM_TILE_BOUND_REF")) c->tb_ref = atoi(e) != 0;
-    for (int v = 0; v < 2; ++v) {
-      int ftx[3], ty[3], sum_tx = 0, max_ty = 1;
-      bool on[3];
-      for (int k = 0; k < 3; ++k) {
-        const LmDet& D = K.det[3 * v + k];
-        ftx[k] = D.kind != 0 ? K.tt_tx[v] : K.fl_tx[v];
-        ty[k] = D.kind != 0 ? K.tt_ty[v] : K.fl_ty[v];
-        on[k] = D.kind != 0 ? c->tailskip_on : c->pointskip_on;
-        if (on[k]) {
-          sum_tx += ftx[k];
-          max_ty = std::max(max_ty, ty[k]);
-        }
-      }
-      const int br0 = std::max(1, LM_TBW_TILES / std::max(1, sum_tx));
-      const int nband = (max_ty + br0 - 1) / br0, br = (max_ty + nband - 1) / nband;
-      K.tbw_br[v] = br;
-      K.tbw_nband[v] = (max_ty + br - 1) / br;
-      // the most window-table entries and ext rows of a band, for a set of detectors with a bound
-      auto band_rows = [&](const bool (&use)[3]) {
-        int rows = 0;
-        for (int j = 0; j < K.tbw_nband[v]; ++j) {
-          int y_lo = K.ext_h[v], y_hi = 0;
-          for (int k = 0; k < 3; ++k) {
-            const LmDet& D = K.det[3 * v + k];
-            int t0, nty;
-            const int ohb = lm_tbw_band(D, ty[k], br, j, &t0, &nty);
-            if (!use[k] || nty == 0) continue;
-            y_lo = std::min(y_lo, D.in_y + LM_FH * t0);
-            y_hi = std::max(y_hi, D.in_y + LM_FH * t0 + ohb + D.kh - 1);
-          }
-          rows = std::max(rows, std::min(y_hi, K.ext_h[v]) - y_lo);
-        }
-        return rows;
-      };
-      auto layout = [&](const bool (&use)[3]) {
-        int b_lo = K.ext_w[v] / LM_TB_BLK, b_hi = 0;
-        for (int k = 0; k < 3; ++k) {
-          const LmDet& D = K.det[3 * v + k];
-          if (!use[k]) continue;
-          b_lo = std::min(b_lo, D.in_x / LM_TB_BLK);
-          b_hi = std::max(b_hi, (D.in_x + D.ow + D.kw - 1 + LM_TB_BLK - 1) / LM_TB_BLK);
-        }
-        b_lo = b_lo / 2 * 2;
-        b_hi = std::min((b_hi + 1) / 2 * 2, K.ext_w[v] / LM_TB_BLK);
-        K.tbw_blo[v] = b_lo < b_hi ? b_lo : 0;
-        K.tbw_nbk[v] = b_lo < b_hi ? b_hi - b_lo : 0;
-        K.tbw_rows[v] = std::max(0, band_rows(use));
-        int64_t o = 2 * (int64_t)K.tbw_rows[v] * K.tbw_nbk[v];
-        K.tbw_v[v] = (int32_t)o;
-        o += 2 * (int64_t)std::max(0, K.tbw_rows[v] - (LM_TB_H - 1)) * K.tbw_nbk[v];
-        // when a detector of the view is refined, the windows become their pair table (lm_tbr_pair_word) in place:
-        // a spare row and three words behind them (a term's words are fetched a chunk ahead, without a clamp), and
-        // per detector the windows' entries at the last block of its window (tbw_rows entries each: one spare)
-        bool pairs = false;
-        for (int k = 0; k < 3; ++k) pairs = pairs || (use[k] && K.tbr_on[3 * v + k] != 0);
-        if (pairs) o += 2 * (int64_t)K.tbw_nbk[v] + 16;
-        K.tbw_al[v] = (int32_t)o;
-        if (pairs) o += 2 * 3 * (int64_t)K.tbw_rows[v];
-        o = (o + 7) / 8 * 8;
-        for (int k = 0; k < 3; ++k) {
-          const int d = 3 * v + k;
-          const LmDet& D = K.det[d];
-          K.tbw_use[d] = use[k] ? 1 : 0;
-          K.tbw_inv[d] = lm_rcp(ftx[k]);
-          K.tbw_pn[d] = (int32_t)o;
-          if (use[k]) o += 16 * (int64_t)D.kh;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const int d = 3 * v + k;
-          const LmDet& D = K.det[d];
-          int wsz = 0;
-          for (int j = 0; use[k] && j < K.tbw_nband[v]; ++j) {
-            int t0, nty;
-            const int ohb = lm_tbw_band(D, ty[k], br, j, &t0, &nty);
-            if (nty) wsz = std::max(wsz, lm_tb_win_rows(ohb, D.kh) * ftx[k]);
-          }
-          K.tbw_win[d] = (int32_t)o;
-          K.tbw_wsz[d] = wsz;
-          o += 2 * (int64_t)wsz;
-        }
-        o = (o + 3) / 4 * 4;
-        for (int k = 0; k < 3; ++k) {
-          K.tbw_ent[3 * v + k] = (int32_t)o;
-          if (on[k]) o += 4 * (int64_t)br * ftx[k];
-        }
-        K.tbw_work[v] = (int32_t)o;
-        o += 4 * (int64_t)br * sum_tx;
-        return o;
-      };
-      // (the tail detector is the last to lose its bound, as in k_tile_bound_ref)
-      bool use[3];
-      // (a thread loads one of a detector's P_i, N_i: kh <= LM_TB_THREADS / 2)
-      for (int k = 0; k < 3; ++k)
-        use[k] = on[k] && K.tb_skip[3 * v + k] != 0 && 2 * K.det[3 * v + k].kh <= LM_TB_THREADS;
-      int64_t lds = layout(use);
-      for (int k : {1, 0, 2}) {
-        if (lds <= kTileBoundWgLds) break;
-        use[k] = false;
-        lds = layout(use);
-      }
-      if (lds > kTileBoundWgLds) throw std::invalid_argument("bounding box too wide for the tile lists' workgroup.");
-      K.tbw_lds[v] = (int32_t)lds;
-      c->tbw_lds = std::max(c->tbw_lds, (size_t)lds);
-    }
-    bool one_chunk = false;
-    for (int d = 0; d < LM_NDET; ++d)
-      one_chunk = one_chunk || (K.tbw_use[d] && K.tbr_on[d] && lm_tbr_chunks(K.tbr_ng[d]) == 1);
-    c->tbw_row_loop = LM_TBW_ROW_LOOP && one_chunk;
-  }
-  // LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
-  // scaled by 2^s so that the largest |w| lands in [2^14, 2^15) (the rounding
-  // is then relative and no weight of interest is subnormal; 2^s and 2^-s
-  // are exact in fp32)
+  return wts;
+}
+
+// LM_CORR_F16: each detector's B fragments (lm_corr.hip k_corr_f16) as f16,
+// scaled by 2^s so that the largest |w| lands in [2^14, 2^15) (the rounding
+// is then relative and no weight of interest is subnormal; 2^s and 2^-s
+// are exact in fp32); empty in the fp32 mode.  Reads det[], M; fills
+// det[].wscale, inv_wscale, w16_off.
+std::vector<_Float16> f16_fragments(LmConst& K, const lm_setup* su, const lm_model* M) {
+  const ModelDets dets = model_dets(M);
   std::vector<_Float16> w16;
   if (su->corr_precision == LM_CORR_F16) {
     for (int d = 0; d < 6; ++d) {
@@ -913,22 +826,30 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
               w16.push_back((_Float16)std::ldexp(f16_bfrag_weight(dets[d]->weights, D.kw, i, c, l, j), sc));
     }
   }
-  uint8_t adj[256];
-  {
-    // imadjust(I, I, 0, 0.6, 0, 1) (LocoMouse_class.cpp:3204-3242)
-    double low_in = 0 * 255, high_in = 0.6 * 255, low_out = 0 * 255, high_out = 1 * 255.0;
-    double range_in = high_in - low_in, range_out = high_out - low_out, range_div = range_out / range_in;
-    for (int i = 0; i < 256; ++i) {
-      double temp;
-      if (i <= low_in) temp = 0;
-      else if (i >= high_in) temp = range_out;
-      else temp = (i - low_in) * (range_div);
-      adj[i] = (uint8_t)std::round((temp + low_out));
-    }
-  }
+  return w16;
+}
 
-  // ---------------- frame-invariant device data (create-time copies on a
-  // temporary stream: see COPY_SYNC)
+// The tail mask's table: imadjust(I, I, 0, 0.6, 0, 1) (LocoMouse_class.cpp:3204-3242).
+void imadjust_table(uint8_t (&adj)[256]) {
+  double low_in = 0 * 255, high_in = 0.6 * 255, low_out = 0 * 255, high_out = 1 * 255.0;
+  double range_in = high_in - low_in, range_out = high_out - low_out, range_div = range_out / range_in;
+  for (int i = 0; i < 256; ++i) {
+    double temp;
+    if (i <= low_in) temp = 0;
+    else if (i >= high_in) temp = range_out;
+    else temp = (i - low_in) * (range_div);
+    adj[i] = (uint8_t)std::round((temp + low_out));
+  }
+}
+
+// The frame-invariant device data (create-time copies on a temporary stream:
+// see COPY_SYNC) and the kernels' LDS attributes: the only step that touches
+// HIP.  Reads the setup's background and calibration map, the tables of the
+// steps before and c->K; fills the context's device buffers and fstride.
+void upload_constants(lm_ctx* c, const lm_setup* su, const std::vector<float>& wts, const std::vector<double>& tbc,
+                      const std::vector<_Float16>& w16, const uint8_t (&adj)[256]) {
+  const int64_t nv = (int64_t)su->video_rows * su->video_cols;
+  const int64_t nc = (int64_t)su->calib_rows * su->calib_cols;
   hipStream_t cs = nullptr;
   HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   struct StreamGuard {
@@ -959,6 +880,42 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   for (const auto& P : c->corr_plan)
     for (size_t g = 0; g < P.groups.size(); ++g)
       HIPCHK(hipFuncSetAttribute(P.groups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds[g]));
+}
+
+void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const lm_model* M) {
+  check_inputs(su, P, M);
+  const LmTileSwitches sw = read_switches(c, su);
+  c->setup = *su;
+  c->params = *P;
+  c->geo = make_geometry(su, P, M);
+  const lm_geometry& g = c->geo;
+  const lm_rect ub = P->bounding_box_bottom, us = P->bounding_box_side;
+  c->bb_x = ub.x + ub.width;  // getBoundingBox provided-box branch (:547-557)
+  c->bb_ys = us.y + us.height;
+  c->bb_yb = ub.y + ub.height;
+  c->npix = (int)((int64_t)su->video_rows * su->video_cols);
+
+  // the kernel constants (zeroed first: the upload is byte-deterministic)
+  LmConst& K = c->K;
+  std::memset(&K, 0, sizeof(K));
+  const int w_off = fill_detectors(K, g, su, M);
+  fill_image_constants(K, g, su, P);
+  fill_flag_grid(K, c->nslots);
+  plan_tail_lds(c, g);
+  fill_list_and_cost_constants(K, g, P, M);
+  slot_sizes(c);
+  build_corr_plans(c, su);
+  const std::vector<float> wts = pad_weights(K, M, w_off);
+  const LmTilePlan plan = lm_tile_plan(K, c->nslots, wts.data(), sw);  // (lm_tile_plan.h)
+  c->tailskip_on = plan.tailskip;
+  c->pointskip_on = plan.pointskip;
+  c->tb_lds = plan.tb_lds;
+  c->tbw_lds = plan.tbw_lds;
+  c->tbw_row_loop = plan.row_loop;
+  const std::vector<_Float16> w16 = f16_fragments(K, su, M);
+  uint8_t adj[256];
+  imadjust_table(adj);
+  upload_constants(c, su, wts, plan.tbc, w16, adj);
 }
 
 

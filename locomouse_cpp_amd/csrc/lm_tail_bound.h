@@ -1,6 +1,6 @@
 /*
  * lm_tail_bound.h — an upper bound on a detector's scores over one 40 x 4
- * output tile, from per-row pixel ranges (plain C++: the host runtime, the
+ * output tile, from per-row pixel ranges (plain C++: the host runtime's plan lm_tile_plan.h, the
  * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
  * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp,
  * tests/cpp/tile_refine_check.cpp, tests/cpp/tile_pair_check.cpp and
