@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lm_corr_dir.h"
 #include "lm_device.h"
 
 #define LM_CORR_THREADS 192
@@ -154,7 +155,16 @@ struct CorrDark {
 hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t lds, hipStream_t st, const LmConst* K,
                        const LmDetGroup& G, const uint8_t* ext, int64_t ext_slot_bytes, const void* weights, int s0,
                        unsigned long long* keys, int32_t* n_pos, uint8_t* tailbin, int64_t tailbin_slot_bytes,
-                       const CorrDark& dark);
+                       const CorrDark& dark, const LmCorrDirRec* dir);
+// The batch's wave directory for the ring launches (k_corr_dir, once per batch
+// after the lists are final): record b of `out` for launch group b of the
+// plan (`ring`: the group is a ring launch; nslots: the batch's processed
+// slots, launch_corr's grid.y).  launch_corr's `dir` is the group's record,
+// or null: the waves walk the group's detectors (LM_CORR_DIR=0).  A group
+// whose waves exceed its grid sets LM_DEVERR_CORR_DIR in the lane's error word.
+#define LM_DEVERR_CORR_DIR 64
+hipError_t launch_corr_dir(hipStream_t st, const LmConst* K, const LmDetGroup* groups, const char* ring, int ngroups,
+                           int nslots, const CorrDark& dark, LmCorrDirRec* out, int32_t* err);
 // Diagnostics: raw scores of every detector of slots s0 .. s0 + grid.y - 1.
 hipError_t launch_corr_dbg(bool unf, dim3 grid, hipStream_t st, const LmConst* K, const uint8_t* ext,
                            int64_t ext_slot_bytes, const float* weights, int s0, float* dbg, const int64_t* dbg_off,

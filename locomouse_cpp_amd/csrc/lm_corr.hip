@@ -15,6 +15,9 @@
 //                       width of LM_KW_LIST, any height): one wave per 80 x 16
 //                       output tile streaming its window through a private
 //                       LDS ring; the production path.
+//   k_corr_dir          once per batch: the waves of each ring launch's
+//                       detectors (lm_corr_dir.h), so a ring wave finds its
+//                       work, or that it has none, from one scalar load.
 //   k_corr_gen<UNF>     any width and height: taps in chunks of 4 columns and
 //                       the tap rows in LDS-sized chunks (detectors larger than
 //                       the LDS window, widths without an instantiation).
@@ -239,28 +242,43 @@ struct RwRun {
 };
 
 // Wave g of a ring launch -> its detector and sub-tiles.  The batch's work
-// is flattened detector-major (all slots of the group's first detector, then
+// is flattened detector-major (all waves of the group's first detector, then
 // the next ...; the host puts the longest detectors first), so no wave idles
-// at a frame's end.  With dark-tile lists (tl_cnt != nullptr) a point
-// detector's waves take its view's bright LM_FW x LM_FH tiles LM_RW_NQ at a
-// time from the list segments k_ingest filled (segment c: tl_cnt[view
-// LM_TL_NC + c] tiles, ceil(/ LM_RW_NQ) waves), packed densely: a wave finds
-// its segment with one scan over the 64 counters, one per lane.  With
-// per-detector point lists (tl_per_det: tl_cnt / tl_list are k_tile_bound's,
-// indexed by list id) the waves take the detector's own tiles instead: its
-// view's bright tiles that are not proven non-positive, a subset of them, in
-// the same segments.  With tail-tile lists (tt_cnt != nullptr) a tail
-// detector's waves take the tiles k_tile_bound could not prove non-positive
-// from its segments in the same way.
-// The group's wave count is known on the device only, so the grid is
-// sized for every 80 x 16 tile and the waves past the last group's count
-// (whole workgroups at the grid's end) return.  That is enough: a segment
-// holds the tiles of whole slots, a slot lists at most the 8 sub-tile places
-// of each of its nt 80 x 16 tiles (edge tiles fewer), so a segment of k slots
-// needs at most ceil(8 nt k / 8) = nt k waves, and the segments' slots add
-// up to the batch's.  Otherwise a wave takes the sub-tiles of one
-// 80 x 16 tile (row-major per slot).  Called by every lane of the wave;
-// false: past the last wave.
+// at a frame's end.
+//
+// A detector's waves.  Listed (corr_det_list gives a list): its tiles come
+// LM_RW_NQ at a time from the 64 segments of a list, segment c holding cnt[c]
+// LM_FW x LM_FH tiles and so ceil(cnt[c] / LM_RW_NQ) waves, packed densely: a
+// wave finds its segment with one scan over the 64 counters, one per lane.
+// The list is, for a point detector, its view's bright tiles (k_ingest's,
+// tl_cnt / tl_list indexed by view) or, with per-detector point lists
+// (tl_per_det: tl_cnt / tl_list are k_tile_bound's, indexed by list id), its
+// own: the view's bright tiles that are not proven non-positive, a subset in
+// the same segments; for a tail detector (tt_cnt != nullptr) the tiles
+// k_tile_bound could not prove non-positive.  Unlisted (LM_CORR_DARK=0,
+// LM_CORR_TAILSKIP=0 or LM_CORR_POINTSKIP=0 took the list away): one wave per
+// 80 x 16 tile and slot, row-major per slot.  lm_corr_dir.h holds the
+// arithmetic of both.
+//
+// The group's wave count is known on the device only, so the grid is sized
+// for every 80 x 16 tile and the waves past the group's count return.  That
+// is enough: a segment holds the tiles of whole slots, a slot lists at most
+// the 8 sub-tile places of each of its nt 80 x 16 tiles (edge tiles fewer),
+// so a segment of k slots needs at most ceil(8 nt k / 8) = nt k waves, and
+// the segments' slots add up to the batch's.  k_corr_dir checks it.
+//
+// With the tile skips most of that grid is empty (C3: about 3,600 of 19,000
+// workgroups find a tile), and a wave that walks the group's detectors to
+// learn so pays one dependent global round trip per listed detector while
+// its workgroup holds its ring LDS.  So k_corr_dir, once per batch before the
+// correlation, writes one LmCorrDirRec per launch group: the cumulative waves
+// of the group's detectors.  A wave reads its group's record with one scalar
+// load; past the total it returns before any vector load, otherwise scalar
+// compares give its detector and only that detector's 64 counters are loaded
+// and scanned (corr_locate_dir).  Without a record (LM_CORR_DIR=0) the wave
+// walks the detectors in order (corr_locate_walk).  Both give wave g the same
+// detector, segment, place and tiles: they share every step but the search
+// for the detector (tests/cpp/corr_dir_check.cpp replays both).
 //
 // Round 6 tried an arithmetic map instead (workgroup b -> the room of its
 // slot group's segment, the counter and the entries read together: one
@@ -270,10 +288,60 @@ struct RwRun {
 // three wave slots while its LDS is held, and the empty workgroups sit
 // between the working ones; the dense layout has neither.
 static_assert(LM_TL_NC == 64, "one list counter per lane");
-DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
-                        const uint32_t* tl_list, int tl_per_det, const int32_t* tt_cnt, const uint32_t* tt_list, int& d,
-                        RwRun& R) {
+
+// The list a ring launch takes detector D's tiles from.
+struct CorrList {
+  const int32_t* cnt;   // its LM_TL_NC segment counters; nullptr: unlisted, every 80 x 16 tile is computed
+  const uint32_t* lst;  // its entries
+  int ftx, ntile;       // columns and tiles of the tile grid the entries index
+};
+DEV CorrList corr_det_list(const LmConst& K, const LmDet& D, const int32_t* tl_cnt, const uint32_t* tl_list, int tl_per_det,
+                           const int32_t* tt_cnt, const uint32_t* tt_list) {
+  const bool pt = tl_cnt != nullptr && D.kind == 0;    // bright tiles of the view
+  if (!pt && !(tt_cnt != nullptr && D.kind != 0))      // or the tail detector's tiles that are not proven
+    return CorrList{nullptr, nullptr, 0, 0};
+  const int v = pt ? D.view : D.list;             // the tile grid (a view's, or a tail detector's)
+  const int li = pt && !tl_per_det ? v : D.list;  // the list: the view's, or the detector's own
+  const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], ntile = ftx * (pt ? K.fl_ty[v] : K.tt_ty[v]);
+  const uint32_t* lst = pt ? tl_list + (int64_t)li * K.tl_stride : tt_list + (int64_t)li * K.tt_stride;
+  return CorrList{(pt ? tl_cnt : tt_cnt) + li * LM_TL_NC, lst, ftx, ntile};
+}
+
+// Inclusive scan over the wave's lanes: waves of segments 0 .. lane (lane 63: the detector's).
+DEV int corr_scan_waves(int wv) {
+  const int lane = threadIdx.x & 63;
+  int P = wv;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(P, o);
+    if (lane >= o) P += u;
+  }
+  return P;
+}
+
+// Wave `local` of a listed detector (cn: the lane's counter, wv: its waves, P: their scan).
+DEV RwRun corr_listed_run(const CorrList& Ls, int cn, int wv, int P, int local, int nslots) {
   constexpr int NQ = LM_RW_NQ;
+  const int c = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(P > local)) - 1);
+  const int w = local - (__builtin_amdgcn_readlane(P, c) - __builtin_amdgcn_readlane(wv, c));  // place in segment c
+  const int ng = (nslots + LM_INGEST_FB - 1) / LM_INGEST_FB;
+  return RwRun{Ls.lst + (int64_t)lm_tl_y0(c, ng) * LM_INGEST_FB * Ls.ntile + NQ * w,
+               min(NQ, __builtin_amdgcn_readlane(cn, c) - NQ * w), Ls.ftx, 0, 0, 0};
+}
+
+// Wave `local` of an unlisted detector of nt 80 x 16 tiles per slot.
+DEV RwRun corr_unlisted_run(const LmDet& D, int nt, int s0, int local) {
+  const int tx = D.tiles_x;
+  const int lt = local - (local / nt) * nt;
+  return RwRun{nullptr, LM_RW_NQ, 0, s0 + local / nt, (lt / tx) * LM_RW_TH, (lt % tx) * LM_TW};
+}
+
+// The walk: detector by detector, each listed one with a load of its counters
+// and a scan before the next is looked at.  Called by every lane of the wave;
+// false: past the last wave.
+DEV bool corr_locate_walk(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
+                          const uint32_t* tl_list, int tl_per_det, const int32_t* tt_cnt, const uint32_t* tt_list, int& d,
+                          RwRun& R) {
   const int lane = threadIdx.x & 63;
   int base = 0;
 #pragma unroll
@@ -282,46 +350,102 @@ DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s
     const int dk = G.ids[k];
     const LmDet& D = K.det[dk];
     const int nt = G.tile_end[k] - (k ? G.tile_end[k - 1] : 0);
-    const bool pt = tl_cnt != nullptr && D.kind == 0;  // bright tiles of the view
-    if (pt || (tt_cnt != nullptr && D.kind != 0)) {    // or the tail detector's tiles that are not proven
-      const int v = pt ? D.view : D.list;  // the tile grid (a view's, or a tail detector's)
-      const int li = pt && !tl_per_det ? v : D.list;  // the list: the view's, or the detector's own
-      const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], ntile = ftx * (pt ? K.fl_ty[v] : K.tt_ty[v]);
-      const uint32_t* lst = pt ? tl_list + (int64_t)li * K.tl_stride : tt_list + (int64_t)li * K.tt_stride;
-      const int cn = (pt ? tl_cnt : tt_cnt)[li * LM_TL_NC + lane];  // segment `lane`'s tiles
-      const int wv = (cn + NQ - 1) / NQ;
-      int P = wv;  // inclusive scan: waves of segments 0 .. lane
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(P, o);
-        if (lane >= o) P += u;
-      }
+    const CorrList Ls = corr_det_list(K, D, tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list);
+    if (Ls.cnt) {
+      const int cn = Ls.cnt[lane];  // segment `lane`'s tiles
+      const int wv = lm_cd_seg_waves(cn);
+      const int P = corr_scan_waves(wv);
       const int cnt = __builtin_amdgcn_readlane(P, 63);  // (readlane: wave-uniform values stay scalar)
       if (g < base + cnt) {
-        const int local = g - base;
-        const int c = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(P > local)) - 1);
-        const int w = local - (__builtin_amdgcn_readlane(P, c) - __builtin_amdgcn_readlane(wv, c));  // place in segment c
-        const int ng = (nslots + LM_INGEST_FB - 1) / LM_INGEST_FB;
         d = dk;
-        R = RwRun{lst + (int64_t)lm_tl_y0(c, ng) * LM_INGEST_FB * ntile + NQ * w,
-                  min(NQ, __builtin_amdgcn_readlane(cn, c) - NQ * w), ftx, 0, 0, 0};
+        R = corr_listed_run(Ls, cn, wv, P, g - base, nslots);
         return true;
       }
       base += cnt;
     } else {
-      const int cnt = nt * nslots;
+      const int cnt = lm_cd_unlisted_waves(nt, nslots);
       if (g < base + cnt) {
-        const int local = g - base;
-        const int tx = D.tiles_x;
-        const int lt = local - (local / nt) * nt;
         d = dk;
-        R = RwRun{nullptr, NQ, 0, s0 + local / nt, (lt / tx) * LM_RW_TH, (lt % tx) * LM_TW};
+        R = corr_unlisted_run(D, nt, s0, g - base);
         return true;
       }
       base += cnt;
     }
   }
   return false;
+}
+
+// By the group's directory record (k_corr_dir): one scalar load, then the
+// wave's own detector alone.
+DEV bool corr_locate_dir(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
+                         const uint32_t* tl_list, int tl_per_det, const int32_t* tt_cnt, const uint32_t* tt_list,
+                         const LmCorrDirRec* __restrict__ dir, int& d, RwRun& R) {
+  // (as one vector: the record's eight words in one s_load_dwordx8, not the total first and the ends after it)
+  typedef int32_t lm_i8 __attribute__((ext_vector_type(8)));
+  static_assert(LM_NDET == 6, "the record's words");
+  const lm_i8 rv = *reinterpret_cast<const lm_i8*>(dir);
+  const LmCorrDirRec rec{{rv[0], rv[1], rv[2], rv[3], rv[4], rv[5]}, rv[6], rv[7]};
+  int k, local;
+  if (!lm_cd_lookup(rec, G.n, g, &k, &local)) return false;
+  // (G has to be the kernel's own argument, read from the kernel's argument segment: indexing a copy of it in a
+  // local struct by k puts that whole struct into scratch memory)
+  const int dk = G.ids[k], t0 = k ? G.tile_end[k - 1] : 0, t1 = G.tile_end[k];
+  const LmDet& D = K.det[dk];
+  const CorrList Ls = corr_det_list(K, D, tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list);
+  d = dk;
+  if (Ls.cnt) {
+    const int cn = Ls.cnt[threadIdx.x & 63];
+    const int wv = lm_cd_seg_waves(cn);
+    R = corr_listed_run(Ls, cn, wv, corr_scan_waves(wv), local, nslots);
+  } else {
+    R = corr_unlisted_run(D, t1 - t0, s0, local);
+  }
+  return true;
+}
+
+DEV bool corr_locate_rw(const LmConst& K, const LmDetGroup& G, int nslots, int s0, int g, const int32_t* tl_cnt,
+                        const uint32_t* tl_list, int tl_per_det, const int32_t* tt_cnt, const uint32_t* tt_list,
+                        const LmCorrDirRec* __restrict__ dir, int& d, RwRun& R) {
+  if (dir) return corr_locate_dir(K, G, nslots, s0, g, tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list, dir, d, R);
+  return corr_locate_walk(K, G, nslots, s0, g, tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list, d, R);
+}
+
+// The directory of a batch: workgroup b (one wave) writes launch group b's
+// record from the same counters and the same list choice the correlation's
+// waves will see, and flags a group whose waves exceed its grid (the argument
+// above says none does; the waves past the grid would be lost silently).
+struct LmCorrDirGroups {
+  int32_t n;
+  int32_t ring[LM_NDET];  // group b is a ring launch (the others get an empty record)
+  LmDetGroup g[LM_NDET];
+};
+__global__ __launch_bounds__(64) void k_corr_dir(const LmConst* __restrict__ Kp, const LmCorrDirGroups A, int nslots,
+                                                  const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list,
+                                                  int tl_per_det, const int32_t* __restrict__ tt_cnt,
+                                                  const uint32_t* __restrict__ tt_list, LmCorrDirRec* __restrict__ out,
+                                                  int32_t* __restrict__ err) {
+  const LmConst& K = *Kp;
+  const int b = blockIdx.x;
+  const LmDetGroup& G = A.g[b];
+  const int n = A.ring[b] ? G.n : 0;
+  const int lane = threadIdx.x;
+  int32_t waves[LM_NDET];
+#pragma unroll
+  for (int k = 0; k < LM_NDET; ++k) {
+    waves[k] = 0;
+    if (k < n) {
+      const CorrList Ls = corr_det_list(K, K.det[G.ids[k]], tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list);
+      if (Ls.cnt)
+        waves[k] = __builtin_amdgcn_readlane(corr_scan_waves(lm_cd_seg_waves(Ls.cnt[lane])), 63);
+      else
+        waves[k] = lm_cd_unlisted_waves(G.tile_end[k] - (k ? G.tile_end[k - 1] : 0), nslots);
+    }
+  }
+  if (lane == 0) {
+    const LmCorrDirRec rec = lm_cd_record(waves, n);
+    out[b] = rec;
+    if (n > 0 && rec.total > G.tile_end[n - 1] * nslots) atomicOr(err, LM_DEVERR_CORR_DIR);
+  }
 }
 
 // A workgroup tile of a point detector (k_corr_gen, k_corr_f16) whose flag
@@ -846,7 +970,7 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(K
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
     const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, int tl_per_det,
-    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list) {
+    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list, const LmCorrDirRec* __restrict__ dir) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * rw_ring_floats(KW);
@@ -854,8 +978,8 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(K
                  tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list};
   int d;
   RwRun R;
-  if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, d, R))
+  if (!corr_locate_rw(*a.K, G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
+                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, dir, d, R))
     return;
   rw_tile<KW, UNF>(a, d, R, ring);
 }
@@ -870,7 +994,7 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const float* __restrict__ weights, int s0, int nslots, unsigned long long* __restrict__ keys,
     int32_t* __restrict__ n_pos, uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes,
     const int32_t* __restrict__ tl_cnt, const uint32_t* __restrict__ tl_list, int tl_per_det,
-    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list) {
+    const int32_t* __restrict__ tt_cnt, const uint32_t* __restrict__ tt_list, const LmCorrDirRec* __restrict__ dir) {
   extern __shared__ uint4 lds_rw[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* ring = reinterpret_cast<float*>(lds_rw) + wave * G.ring_floats;
@@ -878,8 +1002,8 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(L
                  tl_cnt, tl_list, tl_per_det, tt_cnt, tt_list};
   int d;
   RwRun R;
-  if (!corr_locate_rw(*a.K, a.G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
-                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, d, R))
+  if (!corr_locate_rw(*a.K, G, a.nslots, a.s0, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, a.tl_cnt,
+                      a.tl_list, a.tl_per_det, a.tt_cnt, a.tt_list, dir, d, R))
     return;
   switch (a.K->det[d].kw_ring) {
 #define LM_KW_CASE(n)           \
@@ -1285,7 +1409,7 @@ const void* corr_kernel_rw_all(bool unf) {
 hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t lds, hipStream_t st, const LmConst* K,
                        const LmDetGroup& G, const uint8_t* ext, int64_t ext_slot_bytes, const void* weights, int s0,
                        unsigned long long* keys, int32_t* n_pos, uint8_t* tailbin, int64_t tailbin_slot_bytes,
-                       const CorrDark& dk) {
+                       const CorrDark& dk, const LmCorrDirRec* dir) {
   if (ring) {
     int nslots = (int)grid.y;
     const unsigned waves = (unsigned)(G.tile_end[G.n - 1] * nslots);  // every 80 x 16 tile (corr_locate_rw)
@@ -1296,13 +1420,28 @@ hipError_t launch_corr(const void* fn, bool ring, dim3 grid, int threads, size_t
     void* args[] = {(void*)&K,       (void*)&G,    (void*)&ext,     (void*)&ext_slot_bytes,
                     (void*)&weights, (void*)&s0,   (void*)&nslots,  (void*)&keys,
                     (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes, (void*)&tl_cnt,
-                    (void*)&tl_list, (void*)&per_det, (void*)&dk.tail_cnt, (void*)&dk.tail_list};
+                    (void*)&tl_list, (void*)&per_det, (void*)&dk.tail_cnt, (void*)&dk.tail_list, (void*)&dir};
     return hipLaunchKernel(fn, dim3((waves + LM_RW_WAVES - 1) / LM_RW_WAVES), dim3(LM_RW_THREADS), args, lds, st);
   }
   void* args[] = {(void*)&K,     (void*)&G,       (void*)&ext,     (void*)&ext_slot_bytes,           (void*)&weights,
                   (void*)&s0,    (void*)&keys,    (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes,
                   (void*)&dk.flags, (void*)&dk.tail_flags, (void*)&dk.pt_flags};
   return hipLaunchKernel(fn, grid, dim3(threads), args, lds, st);
+}
+
+hipError_t launch_corr_dir(hipStream_t st, const LmConst* K, const LmDetGroup* groups, const char* ring, int ngroups,
+                           int nslots, const CorrDark& dk, LmCorrDirRec* out, int32_t* err) {
+  if (ngroups < 1 || ngroups > LM_NDET) return hipErrorInvalidValue;
+  LmCorrDirGroups A{};
+  A.n = ngroups;
+  for (int b = 0; b < ngroups; ++b) {
+    A.ring[b] = ring[b] ? 1 : 0;
+    A.g[b] = groups[b];
+  }
+  const int per_det = dk.pt_cnt != nullptr ? 1 : 0;  // (as launch_corr)
+  k_corr_dir<<<ngroups, 64, 0, st>>>(K, A, nslots, per_det ? dk.pt_cnt : dk.cnt, per_det ? dk.pt_list : dk.list, per_det,
+                                     dk.tail_cnt, dk.tail_list, out, err);
+  return hipGetLastError();
 }
 
 hipError_t launch_corr_dbg(bool unf, dim3 grid, hipStream_t st, const LmConst* K, const uint8_t* ext,

@@ -114,6 +114,7 @@ struct Lane {
   DevBuf<uint32_t> pt_list;
   DevBuf<int32_t> pt_cnt;    // per list id 64 segment counters of listed tiles, then of bright tiles
   DevBuf<uint32_t> rng;      // k_ingest's block ranges for k_tile_bound: one word per 16-byte chunk of ext
+  DevBuf<LmCorrDirRec> corr_dir;  // k_corr_dir's record per launch group of the batch's correlation plan
   HostBuf<int32_t> h_cnt;   // debug bit 1: dark_cnt of the submitted batch, copied on its stream
   bool h_cnt_valid = false;
   DevBuf<long long> kprof;  // LM_KPROF=1: kernel phase timestamps
@@ -230,6 +231,9 @@ struct lm_ctx {
   // LM_TILE_REFINE=0: the tile bound alone decides (no refinement per output
   // block and tap group), in both kernels
   bool tb_refine = true;
+  // LM_CORR_DIR=0: no k_corr_dir; the ring correlation's waves walk their
+  // group's detectors to find their work (lm_corr.hip corr_locate_walk)
+  bool corr_dir_on = true;
   size_t tb_lds = 0;        // k_tile_bound_ref's LDS bytes (the larger view's)
   size_t tbw_lds = 0;       // k_tile_bound's (the larger view's band)
   // a detector that k_tile_bound refines has one chunk of group constants per
@@ -390,8 +394,8 @@ void check_inputs(const lm_setup* su, const lm_params* P, const lm_model* M) {
 
 // The environment's switches, read at every context creation (LM_RW_WIDEN
 // alone is read once per process, in fill_detectors).  Fills the context's
-// kprof_on, dark_on, tb_refine, tb_ref and returns what the tile plan is asked
-// for; tailskip_on / pointskip_on are set from the plan's answer.
+// kprof_on, dark_on, tb_refine, tb_ref, corr_dir_on and returns what the tile
+// plan is asked for; tailskip_on / pointskip_on are set from the plan's answer.
 LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
   auto flag = [](const char* name, bool dflt) {
     const char* v = getenv(name);
@@ -401,6 +405,7 @@ LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
   c->dark_on = flag("LM_CORR_DARK", true);
   c->tb_refine = flag("LM_TILE_REFINE", true);
   c->tb_ref = flag("LM_TILE_BOUND_REF", false);
+  c->corr_dir_on = flag("LM_CORR_DIR", true);
   LmTileSwitches sw;
   sw.tailskip = flag("LM_CORR_TAILSKIP", true);
   sw.pointskip = flag("LM_CORR_POINTSKIP", true);
@@ -974,6 +979,10 @@ void lane_alloc(lm_ctx* c, Lane& L) {
     SET_SYNC(L.rng.p, 0, (size_t)(c->ext_slot_bytes / LM_INGEST_VEC) * ns * sizeof(uint32_t), st);
   }
   L.err.alloc(16);
+  if (c->corr_dir_on) {
+    L.corr_dir.alloc(LM_NDET);
+    SET_SYNC(L.corr_dir.p, 0, LM_NDET * sizeof(LmCorrDirRec), st);
+  }
   L.frame_ptr.alloc(ns);
   L.slots.alloc(ns);
   L.h_slots.alloc(ns);
@@ -1334,6 +1343,14 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
                 dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list);
       T.end();
     }
+    // the ring launches' wave directory, from the lists as the correlation will read them
+    const lm_ctx::CorrPlan& CP = c->corr_plan[P.plan];
+    if (c->corr_dir_on && std::find(CP.ring.begin(), CP.ring.end(), (char)1) != CP.ring.end()) {
+      std::vector<LmDetGroup> groups;
+      for (const auto& grp : CP.groups) groups.push_back(grp.second);
+      HIPCHK(launch_corr_dir(st, dK, groups.data(), CP.ring.data(), (int)groups.size(), nproc, dk, L.corr_dir.p,
+                             L.err.p));
+    }
   }
   if (part == 1 || part < 0) {
     T.begin("k_corr");
@@ -1344,7 +1361,8 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
       const void* w = c->setup.corr_precision == LM_CORR_F16 ? (const void*)c->weights16.p : (const void*)c->weights.p;
       HIPCHK(launch_corr(grp.first, CP.ring[gi], dim3(G.tile_end[G.n - 1], nproc), CP.threads[gi], CP.lds[gi], st, dK,
                          G, L.ext.p, c->ext_slot_bytes, w, s_proc0, L.keys.p, L.npos.p, L.tailbin.p,
-                         c->tailbin_slot_bytes, lane_dark(c, L)));
+                         c->tailbin_slot_bytes, lane_dark(c, L),
+                         c->corr_dir_on && CP.ring[gi] ? L.corr_dir.p + gi : nullptr));
     }
     T.end();
   }
@@ -1765,6 +1783,7 @@ void finish_batch(lm_ctx* c, Lane& L) {
     if (e & 16) throw std::runtime_error("P22D::add_side_candidate_safe: CV_Assert(S >= 0) failed.");
     if (e & 8) throw std::runtime_error("candidate list exceeds the k_post scratch capacity.");
     if (e & 32) throw std::runtime_error("candidate staging overflow.");
+    if (e & LM_DEVERR_CORR_DIR) throw std::runtime_error("correlation: a launch group's listed waves exceed its grid.");
     if (e) throw std::runtime_error("device error flags " + std::to_string(e));
     if (!ph.overflow) break;
     if (attempt >= 3) throw std::runtime_error("result arena overflow persists.");
