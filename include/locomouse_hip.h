@@ -357,6 +357,13 @@ lm_status lm_debug_corr_work(const lm_ctx* ctx, int32_t* out);
  * reads the lane the batch ran on and fails once that lane was reused. */
 lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out);
 
+/* The tile-bound refinement sums a block in fp32 first and in double only
+ * when the fp32 value lies within its proven error margin of zero
+ * (LM_TILE_SCREEN=0 in the environment at lm_ctx_create: in double alone).
+ * *out = the block sums that took the double path, over every batch of the
+ * context since its creation (it waits for the submitted batches to finish). */
+lm_status lm_debug_screen_fallback(lm_ctx* ctx, int64_t* out);
+
 /* The flag bytes behind those counts for frame f of the last collected batch:
  * out[ty * cols + tx] = 1 when tile (ty, tx) of tail detector `view`
  * (0 bottom, 1 side) was listed; rows x cols = ceil(oh / tile height) x

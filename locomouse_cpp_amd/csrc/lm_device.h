@@ -160,6 +160,13 @@ struct LmConst {
   // its tbr_ng[d] tap groups per row; the group constants (lm_tbr_prepare's
   // layout) at tbr_off[d] of the bound constants
   int32_t tbr_on[LM_NDET], tbr_ng[LM_NDET], tbr_off[LM_NDET];
+  // the fp32 screen ahead of the refinement's double sum (lm_tail_bound.h:
+  // lm_tbs_*): tbs_on[d]: detector d's block sums are screened (tbr_on[d],
+  // LM_TILE_SCREEN and lm_tbs_prepare's verdict); its rows of LM_TBS_ROW floats
+  // at tbs_off[d] of the bound constants (an offset in doubles, like tbr_off);
+  // tbs_bf[d], tbs_e[d]: its bias rounded up and its margin
+  int32_t tbs_on[LM_NDET], tbs_off[LM_NDET];
+  float tbs_bf[LM_NDET], tbs_e[LM_NDET];
   // the point detectors' output region per view: output (y, x) has its
   // I_*_MOUSE pixel at ext (fl_my + y, fl_mx + x); fl_oh x fl_ow outputs
   int32_t fl_my[2], fl_mx[2], fl_oh[2], fl_ow[2];

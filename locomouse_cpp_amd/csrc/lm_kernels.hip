@@ -852,8 +852,12 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
 //      windows are turned into after step 3 (3b: entry b is the range over
 //      blocks b and b + 1, which is what a term reads; see there), by a loop
 //      without chunk stepping where the detectors' weight rows are one chunk
-//      of constants each (at most four tap groups: all of C3's; ROWS below);
-//      one compaction then drops the entries of proven tiles from all three
+//      of constants each (at most four tap groups: all of C3's; ROWS below),
+//      and there in fp32 first (lm_tbs_*: one packed FMA per term; only a lane
+//      whose fp32 sum lies within its proven margin of zero takes the double
+//      loop, and tbs_fallback counts those lanes; LM_TILE_SCREEN=0 or a
+//      detector the screen's gate refuses: the double loop alone); one
+//      compaction then drops the entries of proven tiles from all three
 //      segments.
 //   5. One global atomic per (workgroup, detector) on the slot group's segment
 //      counter (the segment index comes from the slot and the batch's slot
@@ -889,7 +893,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
     int32_t* __restrict__ tt_cnt, uint32_t* __restrict__ tt_list, uint8_t* __restrict__ pt_flags,
-    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list) {
+    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list, unsigned long long* __restrict__ tbs_fallback) {
   const LmConst& K = *Kp;
   extern __shared__ __attribute__((aligned(16))) uint8_t tbw_lds[];
   __shared__ int s_n[3], s_b[3], s_m[3], s_base[3], s_nw;
@@ -1166,6 +1170,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       const int kh = D.kh, ng = K.tbr_ng[d], nc = lm_tbr_chunks(ng);
       const double* __restrict__ C = tbc + K.tbr_off[d];
       const double bias = K.tb_bias[d];
+      const float* __restrict__ Cf = reinterpret_cast<const float*>(tbc + K.tbs_off[d]);  // (the screen's rows)
       const int yb = D.in_y + LM_FH * tk0 - y_lo;  // the band's window row 0 among the loaded rows
       const int bl0 = lm_tbr_block0(D.in_x, 0) - K.tbw_blo[v];
       const int bendl = lm_tbr_block_end(D.in_x, D.ow, D.kw, K.ext_w[v] / LM_TB_BLK) - K.tbw_blo[v];
@@ -1183,7 +1188,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       // (rows > 0: a detector of one chunk per row and `rows` tap groups, lm_tbr_sum_rows_n -- a row's words and
       // alone entry lie a fixed nw words and one entry behind the row's before it, and the row's last term is the
       // detector's last group; rows 0: any detector, lm_tbr_sum)
-      auto level_v = [&](auto rows) {
+      auto level_v = [&](auto rows, auto screen) {
         const uint32_t* pw = V + row0 * nw + (ba0 >> 1);
         const uint16_t* alone = AL + k * als + row0;  // the windows' last block of the detector's window, alone:
         const bool clipped = ba0 + ng == bendl;       // what the last group reads when it stands there
@@ -1200,16 +1205,21 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
         fetch();
         if constexpr (decltype(rows)::value > 0) {
           constexpr int NG = decltype(rows)::value;  // (== ng: the row's last term is known where it is read)
-          return lm_tbr_sum_rows_n<NG>(kh, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
-                   if (g == 0) {  // the row's entries, and the next row's words on their way
-                     lm_tbr_quad_align(w0, w1, w2, ba0, x0, x1);
-                     q = qn;
-                     pw += nw;
-                     alone += 1;
-                     fetch();
-                   }
-                   lm_tbr_quad_get(x0, x1, g, g == NG - 1 && clipped, q, M, m);
-                 }) < 0.0;
+          auto term = [&](int i, int g, unsigned& M, unsigned& m) {
+            if (g == 0) {  // the row's entries, and the next row's words on their way
+              lm_tbr_quad_align(w0, w1, w2, ba0, x0, x1);
+              q = qn;
+              pw += nw;
+              alone += 1;
+              fetch();
+            }
+            lm_tbr_quad_get(x0, x1, g, g == NG - 1 && clipped, q, M, m);
+          };
+          // the fp32 screen of the same terms (-1 proven, 1 unproven, 0 undecided), or the double sum (-1, 1)
+          if constexpr (decltype(screen)::value)
+            return lm_tbs_decide(lm_tbs_sum_rows_n<NG>(kh, Cf, K.tbs_bf[d], term), K.tbs_e[d]);
+          else
+            return lm_tbr_sum_rows_n<NG>(kh, C, bias, term) < 0.0 ? -1 : 1;
         }
         return lm_tbr_sum_negative(kh, ng, C, bias, [&](int i, int g, unsigned& M, unsigned& m) {
           if (g % LM_TBR_GC == 0) {  // a chunk's first term: its entries, and the next chunk's words on their way
@@ -1223,7 +1233,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
             fetch();
           }
           lm_tbr_quad_get(x0, x1, g % LM_TBR_GC, lastc && clipped && g % LM_TBR_GC == jl, q, M, m);
-        });
+        }) ? -1 : 1;
       };
       // rows rs .. rs + nn - 1 from the block ranges B
       auto level_b = [&](int rs, int nn) {
@@ -1240,17 +1250,36 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
         });
       };
       using std::integral_constant;
+      using std::false_type;
+      using std::true_type;
       bool proven;
       if constexpr (!ROWS) {
-        proven = nr == LM_TB_H && level_v(integral_constant<int, 0>{});
-      } else {  // (nc and ng are uniform: a wave takes one of the loops)
+        proven = nr == LM_TB_H && level_v(integral_constant<int, 0>{}, false_type{}) < 0;
+      } else {  // (nc, ng and the screen's flag are uniform: a wave takes one of the loops)
         proven = false;
         if (nr != LM_TB_H) {
-        } else if (nc != 1) proven = level_v(integral_constant<int, 0>{});
-        else if (ng == 4) proven = level_v(integral_constant<int, 4>{});
-        else if (ng == 3) proven = level_v(integral_constant<int, 3>{});
-        else if (ng == 2) proven = level_v(integral_constant<int, 2>{});
-        else proven = level_v(integral_constant<int, 1>{});
+        } else if (nc != 1) proven = level_v(integral_constant<int, 0>{}, false_type{}) < 0;
+        else {
+          // the screen first; the lanes it leaves undecided (few: DESIGN.md section 12) take the double sum, as every
+          // lane of a detector without the screen does, and a wave that has such lanes counts them
+          int dec = 0;
+          if (K.tbs_on[d] != 0) {
+            if (ng == 4) dec = level_v(integral_constant<int, 4>{}, true_type{});
+            else if (ng == 3) dec = level_v(integral_constant<int, 3>{}, true_type{});
+            else if (ng == 2) dec = level_v(integral_constant<int, 2>{}, true_type{});
+            else dec = level_v(integral_constant<int, 1>{}, true_type{});
+            const unsigned long long und = __ballot(dec == 0);
+            if (und != 0ull && (tid & (WV - 1)) == __ffsll((long long)und) - 1)
+              atomicAdd(tbs_fallback, (unsigned long long)__popcll(und));
+          }
+          if (dec == 0) {
+            if (ng == 4) dec = level_v(integral_constant<int, 4>{}, false_type{});
+            else if (ng == 3) dec = level_v(integral_constant<int, 3>{}, false_type{});
+            else if (ng == 2) dec = level_v(integral_constant<int, 2>{}, false_type{});
+            else dec = level_v(integral_constant<int, 1>{}, false_type{});
+          }
+          proven = dec < 0;
+        }
       }
       if (!proven && !(LM_TB_RH == LM_TB_H && nr == LM_TB_H)) {
         if (LM_TB_RH == LM_TB_H) {

@@ -231,6 +231,9 @@ struct lm_ctx {
   // LM_TILE_REFINE=0: the tile bound alone decides (no refinement per output
   // block and tap group), in both kernels
   bool tb_refine = true;
+  // LM_TILE_SCREEN=0: the refinement's block sums in double alone (no fp32
+  // screen ahead of them, lm_tail_bound.h: lm_tbs_*)
+  bool tb_screen = true;
   // LM_CORR_DIR=0: no k_corr_dir; the ring correlation's waves walk their
   // group's detectors to find their work (lm_corr.hip corr_locate_walk)
   bool corr_dir_on = true;
@@ -242,7 +245,12 @@ struct lm_ctx {
   // others' with the generic loop); none has: k_tile_bound<false>, the generic
   // loop alone
   bool tbw_row_loop = false;
-  DevBuf<double> tb_const;  // the bound's P_i, N_i per detector (LmConst::tb_off), then its P[i][g], N[i][g] (tbr_off)
+  // the bound's P_i, N_i per detector (LmConst::tb_off), then its P[i][g], N[i][g] (tbr_off) and the screen's float
+  // rows (tbs_off)
+  DevBuf<double> tb_const;
+  // lanes of k_tile_bound's refinement that the screen left undecided (they took the double sum), over every batch
+  // of the context since its creation (lm_debug_screen_fallback)
+  DevBuf<unsigned long long> tbs_fallback;
   // pipeline
   std::vector<std::unique_ptr<Lane>> lanes;
   DevBuf<uint8_t> handoff;     // two frames: the last frame of submitted batch k in slot k & 1
@@ -394,7 +402,7 @@ void check_inputs(const lm_setup* su, const lm_params* P, const lm_model* M) {
 
 // The environment's switches, read at every context creation (LM_RW_WIDEN
 // alone is read once per process, in fill_detectors).  Fills the context's
-// kprof_on, dark_on, tb_refine, tb_ref, corr_dir_on and returns what the tile
+// kprof_on, dark_on, tb_refine, tb_screen, tb_ref, corr_dir_on and returns what the tile
 // plan is asked for; tailskip_on / pointskip_on are set from the plan's answer.
 LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
   auto flag = [](const char* name, bool dflt) {
@@ -404,12 +412,14 @@ LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
   c->kprof_on = flag("LM_KPROF", false);
   c->dark_on = flag("LM_CORR_DARK", true);
   c->tb_refine = flag("LM_TILE_REFINE", true);
+  c->tb_screen = flag("LM_TILE_SCREEN", true);
   c->tb_ref = flag("LM_TILE_BOUND_REF", false);
   c->corr_dir_on = flag("LM_CORR_DIR", true);
   LmTileSwitches sw;
   sw.tailskip = flag("LM_CORR_TAILSKIP", true);
   sw.pointskip = flag("LM_CORR_POINTSKIP", true);
   sw.refine = c->tb_refine;
+  sw.screen = c->tb_screen;
   sw.f16 = su->corr_precision == LM_CORR_F16;
   sw.dark = c->dark_on;
   return sw;
@@ -869,6 +879,8 @@ void upload_constants(lm_ctx* c, const lm_setup* su, const std::vector<float>& w
   COPY_SYNC(c->weights.p, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice, cs);
   c->tb_const.alloc(tbc.size());
   COPY_SYNC(c->tb_const.p, tbc.data(), tbc.size() * sizeof(double), hipMemcpyHostToDevice, cs);
+  c->tbs_fallback.alloc(1);
+  SET_SYNC(c->tbs_fallback.p, 0, sizeof(unsigned long long), cs);
   if (!w16.empty()) {
     c->weights16.alloc(w16.size());
     COPY_SYNC(c->weights16.p, w16.data(), w16.size() * sizeof(_Float16), hipMemcpyHostToDevice, cs);
@@ -1340,7 +1352,7 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
         (c->tbw_row_loop ? k_tile_bound<true> : k_tile_bound<false>)
             <<<dim3((unsigned)nproc, (unsigned)(K.tbw_nband[0] + K.tbw_nband[1])), LM_TB_THREADS, c->tbw_lds, st>>>(
                 dK, L.rng.p, c->ext_slot_bytes / LM_INGEST_VEC, s_proc0, nproc, c->tb_const.p, dk.flags, dk.tail_flags,
-                dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list);
+                dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list, c->tbs_fallback.p);
       T.end();
     }
     // the ring launches' wave directory, from the lists as the correlation will read them
@@ -2116,6 +2128,19 @@ LM_API lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out) {
       out[2 * t] = std::accumulate(h + t * LM_TL_NC, h + (t + 1) * LM_TL_NC, 0);
       out[2 * t + 1] = ctx->delivered.slots * ctx->K.tt_tx[t] * ctx->K.tt_ty[t];
     }
+  });
+}
+
+LM_API lm_status lm_debug_screen_fallback(lm_ctx* ctx, int64_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  *out = 0;
+  if (ctx->lanes.empty() || !ctx->tbs_fallback.p) return LM_OK;
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    for (const auto& L : ctx->lanes) HIPCHK(hipStreamSynchronize(L->stream));  // (every submitted batch has run)
+    unsigned long long h = 0;
+    COPY_SYNC(&h, ctx->tbs_fallback.p, sizeof(h), hipMemcpyDeviceToHost, ctx->lanes[0]->stream);
+    *out = (int64_t)h;
   });
 }
 

@@ -3,11 +3,12 @@
  * output tile, from per-row pixel ranges (plain C++: the host runtime's plan lm_tile_plan.h, the
  * k_tile_bound kernels, tests/cpp/tail_bound_check.cpp,
  * tests/cpp/point_bound_check.cpp, tests/cpp/tile_window_check.cpp,
- * tests/cpp/tile_refine_check.cpp, tests/cpp/tile_pair_check.cpp and
- * tests/cpp/tile_sum_rows_check.cpp share it),
- * and its refinement per 8-column output block and tap group (below,
- * lm_tbr_*).  Written for the tail detectors (hence the name); it serves the
- * point detectors too.
+ * tests/cpp/tile_refine_check.cpp, tests/cpp/tile_pair_check.cpp,
+ * tests/cpp/tile_sum_rows_check.cpp and tests/cpp/tile_screen_check.cpp share it),
+ * its refinement per 8-column output block and tap group (below, lm_tbr_*)
+ * and the fp32 screen in front of the refinement's double sum (lm_tbs_*).
+ * Written for the tail detectors (hence the name); it serves the point
+ * detectors too.
  *
  * The pipeline uses only the sign of a tail score (threshold(> 0), then
  * connected components), and k_ingest zeroes the tail bitmaps, so a tile
@@ -51,6 +52,7 @@
 #ifndef LM_TAIL_BOUND_H
 #define LM_TAIL_BOUND_H
 
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -393,6 +395,161 @@ template <class F>
 LM_TB_HD inline bool lm_tbr_sum_negative(int kh, int ng, const double* C, double bias, F&& rng) {
   return lm_tbr_sum(kh, ng, C, bias, rng) < 0.0;
 }
+// ------------------------------------------------------------------------
+// The fp32 screen of a block's sum (lm_tbs_*).  Only the sign of U is used,
+// and it is almost never close to zero, so a detector of at most LM_TBR_GC tap
+// groups is first summed in fp32: two chains a (from the bias) and b (from 0),
+//     a <- fma(Pf[i][g], M, a),  b <- fma(-Nf[i][g], m, b)   per term, in lm_tbr_sum's order,
+//     U_f = a + b,
+// one packed FMA per term on the device.  With the margin E below
+//     U_f < -E  =>  U_d < 0 (proven),   U_f >= E  =>  U_d >= 0 (unproven),
+// where U_d is lm_tbr_sum's double; only an item with -E <= U_f < E (or a NaN)
+// is undecided and takes the double sum, which stays the definition.
+//
+// The constants (lm_tbs_prepare): Pf the double P[i][g] rounded up to float, Nf
+// the double N[i][g] rounded down, bf the double bias rounded up.  The screen is
+// off (the double sum alone) when a nonzero constant or the bias is below
+// FLT_MIN in magnitude, so every constant used is a normal float or zero and
+//     0 <= Pf - P <= 2 u Pf,  0 <= N - Nf <= 2 u N,  0 <= bf - bias <= 2 u |bias|,  u = 2^-24.
+// S = |bf| + 255 sum (Pf + Nf), n = kh ng terms.
+//
+// The margin.  Let U_x = bias + sum (P M - N m) in exact arithmetic.
+//  1. Constants.  A pixel range is at most 255, so the exact fp32-constant sum
+//     U_fx = bf + sum (Pf M - Nf m) differs from U_x by at most
+//     2 u (|bias| + 255 sum (Pf + N)) <= 2 u (1 + 2 u) S.
+//  2. The fp32 evaluation.  U_f is a sum of the 2 n + 1 values bf, Pf M, -Nf m
+//     by 2 n additions (n per chain and the final one, or any other
+//     association of them), each product rounded on its own or fused into its
+//     addition: every value passes through at most 2 n additions and one
+//     product rounding, so by the running-error bound
+//     |U_f - U_fx| <= gamma_(2n+1) S,  gamma_k = k u / (1 - k u) <= 2 k u for k u <= 1/2,
+//     which holds for n < 2^20 (the screen is off beyond).  No operation
+//     overflows (S < 1e30, or the screen is off).
+//  3. Underflow.  The product of a normal constant and an integer >= 1 does
+//     not underflow; a sum that falls below FLT_MIN is exact unless it is
+//     fused or flushed to zero, and then off by at most 2^-126: 2 n + 1
+//     operations, at most (2 n + 1) 2^-126 < (n + 1) 2.4e-38 in all.
+//  4. The double sum.  U_d is U_x evaluated in double, each term through at
+//     most n + 2 roundings: |U_d - U_x| <= 2 (n + 2) 2^-53 (|bias| + 255 sum (P + N)),
+//     and that sum is below (1 + 4 u) S.
+// 1 + 2 are below 2 (2 n + 3) u S; the margin is
+//     E = 2 (2 n + 4) u S + (1e-12 + (n + 2) 2^-51) S + (n + 1) 2.4e-38,
+// whose spare 2 u S covers the second-order parts of 1 and 4 (16 u^2 S and 8 u
+// (n + 2) 2^-53 S) and the 1e-12 S the rounding of S and E themselves, computed
+// in double and rounded up to float.  Hence |U_f - U_d| <= E for every input.
+#define LM_TBS_ROW (2 * LM_TBR_GC)  // floats of a weight row's constants: (Pf_g, -Nf_g) for g = 0 .. 3; one 32-byte scalar load
+struct LmTbsConst {
+  float bf, E;  // the bias rounded up; the margin
+  int on;       // the detector may be screened
+};
+inline float lm_tbs_up(double x) {  // the smallest float >= x (|x| within the floats' range)
+  float f = (float)x;
+  return (double)f < x ? nextafterf(f, INFINITY) : f;
+}
+inline float lm_tbs_down(double x) { return -lm_tbs_up(-x); }
+// The screen's constants of a detector from lm_tbr_prepare's C and
+// lm_tb_prepare's bias and verdict ok: kh rows of LM_TBS_ROW floats into Cf.
+inline LmTbsConst lm_tbs_prepare(const double* C, int kh, int ng, double bias, int ok, float* Cf) {
+  LmTbsConst R;
+  R.on = ok && ng >= 1 && ng <= LM_TBR_GC ? 1 : 0;
+  const double tiny = 1.17549435082228750797e-38;  // FLT_MIN
+  double sum = 0.0;
+  for (int i = 0; i < kh; ++i)
+    for (int g = 0; g < LM_TBR_GC; ++g) {
+      const double p = g < ng && R.on ? C[i * 2 * LM_TBR_GC + g] : 0.0, n = g < ng && R.on ? C[(i * 2 + 1) * LM_TBR_GC + g] : 0.0;
+      if (!(p - p == 0.0) || !(n - n == 0.0) || (p != 0.0 && p < tiny) || (n != 0.0 && n < tiny) || p > 1e30 || n > 1e30) {
+        R.on = 0;
+        Cf[i * LM_TBS_ROW + 2 * g] = Cf[i * LM_TBS_ROW + 2 * g + 1] = 0.f;
+        continue;
+      }
+      const float pf = lm_tbs_up(p), nf = lm_tbs_down(n);  // (FLT_MIN is a float: nf is normal or zero as well)
+      Cf[i * LM_TBS_ROW + 2 * g] = pf;
+      Cf[i * LM_TBS_ROW + 2 * g + 1] = -nf;
+      sum += (double)pf + (double)nf;
+    }
+  const double ab = bias < 0.0 ? -bias : bias;
+  if (!(bias - bias == 0.0) || (bias != 0.0 && ab < tiny) || ab > 1e30) {
+    R.on = 0;
+    R.bf = 0.f;
+  } else {
+    R.bf = lm_tbs_up(bias);
+  }
+  const double n = (double)kh * (double)ng, af = R.bf < 0.f ? -(double)R.bf : (double)R.bf;
+  const double S = af + 255.0 * sum;
+  const double E = (2.0 * (2.0 * n + 4.0) / 16777216.0 + 1e-12 + (n + 2.0) / 2251799813685248.0) * S + (n + 1.0) * 2.4e-38;
+  if (!(S < 1e30) || !(n < 1048576.0)) R.on = 0;
+  R.E = R.on ? lm_tbs_up(E) : 0.f;
+  return R;
+}
+// Two floats that one packed FMA takes: (a, b) <- (x0 c0 + a, x1 c1 + b), each fused.
+#if defined(__clang__)
+typedef float lm_tbs_f2 __attribute__((ext_vector_type(2)));
+LM_TB_HD inline lm_tbs_f2 lm_tbs_fma2(float x0, float x1, float c0, float c1, lm_tbs_f2 acc) {
+  return __builtin_elementwise_fma(lm_tbs_f2{x0, x1}, lm_tbs_f2{c0, c1}, acc);  // v_pk_fma_f32 on the device
+}
+#else
+struct lm_tbs_f2 {
+  float x, y;
+};
+inline lm_tbs_f2 lm_tbs_fma2(float x0, float x1, float c0, float c1, lm_tbs_f2 acc) {
+  return lm_tbs_f2{fmaf(x0, c0, acc.x), fmaf(x1, c1, acc.y)};
+}
+#endif
+// U_f of a block for a detector of NG <= LM_TBR_GC tap groups: lm_tbr_sum_rows_n's
+// terms in its order (rng as there), the rows two at a time so that a row's
+// constants are fetched one row ahead.
+template <int NG, class F>
+LM_TB_HD inline float lm_tbs_sum_rows_n(int kh, const float* Cf, float bf, F&& rng) {
+  static_assert(LM_TBR_GC == 4 && NG >= 1 && NG <= LM_TBR_GC, "a row is read as four pairs");
+  lm_tbs_f2 acc = {bf, 0.f};
+  auto row = [&](int i, float c0, float c1, float c2, float c3, float c4, float c5, float c6, float c7, auto&& ahead) {
+    unsigned M, m;
+    rng(i, 0, M, m);
+    ahead();
+    acc = lm_tbs_fma2((float)M, (float)m, c0, c1, acc);
+    if (NG > 1) {
+      rng(i, 1, M, m);
+      acc = lm_tbs_fma2((float)M, (float)m, c2, c3, acc);
+    }
+    if (NG > 2) {
+      rng(i, 2, M, m);
+      acc = lm_tbs_fma2((float)M, (float)m, c4, c5, acc);
+    }
+    if (NG > 3) {
+      rng(i, 3, M, m);
+      acc = lm_tbs_fma2((float)M, (float)m, c6, c7, acc);
+    }
+  };
+  if (kh > 0) {
+    const float* q = Cf;
+    float a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5], a6 = q[6], a7 = q[7];
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, b4 = 0.f, b5 = 0.f, b6 = 0.f, b7 = 0.f;
+    for (int i = 0; i < kh; i += 2, q += 2 * LM_TBS_ROW) {
+      // (past the last row the last row's constants once more: a fetch without a branch)
+      const float* qb = q + (i + 1 < kh ? LM_TBS_ROW : 0);
+      row(i, a0, a1, a2, a3, a4, a5, a6, a7,
+          [&] { b0 = qb[0], b1 = qb[1], b2 = qb[2], b3 = qb[3], b4 = qb[4], b5 = qb[5], b6 = qb[6], b7 = qb[7]; });
+      if (i + 1 < kh) {
+        const float* qa = qb + (i + 2 < kh ? LM_TBS_ROW : 0);
+        row(i + 1, b0, b1, b2, b3, b4, b5, b6, b7,
+            [&] { a0 = qa[0], a1 = qa[1], a2 = qa[2], a3 = qa[3], a4 = qa[4], a5 = qa[5], a6 = qa[6], a7 = qa[7]; });
+      }
+    }
+  }
+  return acc.x + acc.y;
+}
+template <class F>
+LM_TB_HD inline float lm_tbs_sum_rows(int kh, int ng, const float* Cf, float bf, F&& rng) {
+  switch (ng) {
+    case 1: return lm_tbs_sum_rows_n<1>(kh, Cf, bf, rng);
+    case 2: return lm_tbs_sum_rows_n<2>(kh, Cf, bf, rng);
+    case 3: return lm_tbs_sum_rows_n<3>(kh, Cf, bf, rng);
+    default: return lm_tbs_sum_rows_n<4>(kh, Cf, bf, rng);
+  }
+}
+// The decision: -1 proven (U_d < 0), 1 unproven (U_d >= 0), 0 undecided.
+LM_TB_HD inline int lm_tbs_decide(float Uf, float E) { return Uf < -E ? -1 : Uf >= E ? 1 : 0; }
+
 // First block (of the view's) that output block xb reads at group 0, and the
 // end of the blocks the window touches (nbw: blocks per view row).
 LM_TB_HD inline int lm_tbr_block0(int in_x, int xb) { return in_x / LM_TB_BLK + xb; }
@@ -418,6 +575,26 @@ LM_TB_HD inline bool lm_tbr_block_skip(const uint8_t* bmax, const uint8_t* bmin,
       m = nb < m ? nb : m;
     }
   });
+}
+// The screen's decision (lm_tbs_decide) for the same block from the same
+// ranges: the host form of what k_tile_bound computes first, term for term.
+LM_TB_HD inline int lm_tbs_block(const uint8_t* bmax, const uint8_t* bmin, int nbw, int in_y, int in_x, int ow, int kh,
+                                 int kw, int y, int nr, int xb, const float* Cf, float bf, float E) {
+  const int b0 = lm_tbr_block0(in_x, xb), bend = lm_tbr_block_end(in_x, ow, kw, nbw);
+  const float Uf = lm_tbs_sum_rows(kh, lm_tbr_groups(in_x, kw), Cf, bf, [&](int i, int g, unsigned& M, unsigned& m) {
+    const int ba = b0 + g, bb = ba + 1 < bend ? ba + 1 : bend - 1;
+    M = 0u;
+    m = 255u;
+    for (int r = 0; r < nr; ++r) {
+      const int row = (in_y + y + i + r) * nbw;
+      const unsigned xa = bmax[row + ba], xb2 = bmax[row + bb], na = bmin[row + ba], nb = bmin[row + bb];
+      M = xa > M ? xa : M;
+      M = xb2 > M ? xb2 : M;
+      m = na < m ? na : m;
+      m = nb < m ? nb : m;
+    }
+  });
+  return lm_tbs_decide(Uf, E);
 }
 // ------------------------------------------------------------------------
 // Range tables as k_tile_bound keeps them: one 16-bit entry M | m << 8 per

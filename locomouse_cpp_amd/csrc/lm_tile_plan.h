@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstring>
 #include <stdexcept>
 #include <vector>
 
@@ -69,6 +70,7 @@ struct LmTileSwitches {
   bool refine;     // refine the tiles the tile bound fails (LM_TILE_REFINE)
   bool f16;        // the f16 correlation: the bound is for the fp32 chain, both skips off
   bool dark;       // dark tiles (LM_CORR_DARK): the point skip starts from k_ingest's bright flags, off without them
+  bool screen = true;  // the refinement's fp32 screen ahead of the double sum (LM_TILE_SCREEN)
 };
 
 struct LmTilePlan {
@@ -123,8 +125,8 @@ inline void lm_tp_grids(LmConst& K, int nslots, bool* tailskip, bool* pointskip)
 // fp32 weights the kernels use), and k_tile_bound_ref's LDS: the view's block
 // ranges, then the row ranges of each detector whose bound is usable and fits
 // (the tail detector first).  Reads det[], ext_h, ext_w, fl_tx, tt_tx; fills
-// tb_off, tb_skip, tb_bias, tb_rng, tb_lds[v], tbr_on, tbr_ng, tbr_off.
-inline void lm_tp_bounds(LmConst& K, int v, const float* wts, bool tailskip, bool pointskip, bool refine,
+// tb_off, tb_skip, tb_bias, tb_rng, tb_lds[v], tbr_on, tbr_ng, tbr_off, tbs_*.
+inline void lm_tp_bounds(LmConst& K, int v, const float* wts, bool tailskip, bool pointskip, bool refine, bool screen,
                          std::vector<double>& tbc) {
   int64_t lds = 2 * (int64_t)K.ext_h[v] * (K.ext_w[v] / LM_TB_BLK);
   bool any = false;
@@ -151,6 +153,20 @@ inline void lm_tp_bounds(LmConst& K, int v, const float* wts, bool tailskip, boo
     if (K.tbr_on[d]) {
       tbc.resize(tbc.size() + (size_t)lm_tbr_const_size(D.kh, K.tbr_ng[d]));
       lm_tbr_prepare(wts + D.w_off, D.kh, D.kw, D.kwp, D.in_x, tbc.data() + K.tbr_off[d]);
+    }
+    // the screen's constants: floats, kept among the doubles (a row is 32 bytes, kept aligned)
+    K.tbs_on[d] = 0;
+    K.tbs_off[d] = (int32_t)tbc.size();
+    K.tbs_bf[d] = K.tbs_e[d] = 0.f;
+    if (K.tbr_on[d] && screen && lm_tbr_chunks(K.tbr_ng[d]) == 1) {
+      static_assert(LM_TBS_ROW * sizeof(float) == 4 * sizeof(double), "a row of the screen's floats is four doubles");
+      std::vector<float> cf((size_t)D.kh * LM_TBS_ROW);
+      const LmTbsConst R = lm_tbs_prepare(tbc.data() + K.tbr_off[d], D.kh, K.tbr_ng[d], K.tb_bias[d], 1, cf.data());
+      tbc.resize(tbc.size() + cf.size() / 2);
+      std::memcpy(tbc.data() + K.tbs_off[d], cf.data(), cf.size() * sizeof(float));
+      K.tbs_on[d] = R.on;
+      K.tbs_bf[d] = R.bf;
+      K.tbs_e[d] = R.E;
     }
   }
   K.tb_lds[v] = any ? (int32_t)lds : 0;
@@ -308,7 +324,7 @@ inline LmTilePlan lm_tile_plan(LmConst& K, int nslots, const float* wts, const L
   if (!sw.dark) R.pointskip = false;             // it starts from k_ingest's bright flags
   lm_tp_grids(K, nslots, &R.tailskip, &R.pointskip);
   for (int v = 0; v < 2; ++v) {
-    lm_tp_bounds(K, v, wts, R.tailskip, R.pointskip, sw.refine, R.tbc);
+    lm_tp_bounds(K, v, wts, R.tailskip, R.pointskip, sw.refine, sw.screen, R.tbc);
     R.tb_lds = std::max(R.tb_lds, (size_t)K.tb_lds[v]);
   }
   for (int v = 0; v < 2; ++v) {

@@ -28,7 +28,7 @@ EXPORTED = (
     "lm_detect_submit", "lm_detect_submit_device", "lm_detect_collect", "lm_ctx_lanes", "lm_ctx_pending",
     "lm_debug_corr_work", "lm_debug_batch_slots", "lm_debug_dark_tile_width",
     "lm_debug_dark_tile_height", "lm_debug_tail_work", "lm_debug_tail_tiles", "lm_debug_point_work",
-    "lm_debug_point_tiles",
+    "lm_debug_point_tiles", "lm_debug_screen_fallback",
 )
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -202,6 +202,7 @@ def lib():
         L.lm_debug_tail_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
         L.lm_debug_point_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.lm_debug_point_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+        L.lm_debug_screen_fallback.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.lm_debug_batch_slots.argtypes = [C.c_void_p]
         L.lm_debug_batch_slots.restype = C.c_int32
         L.lm_synth_frames_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
@@ -426,6 +427,14 @@ class Context:
         out = (C.c_int32 * 4)()
         _check(lib().lm_debug_tail_work(self._h, out))
         return None if out[0] < 0 else {"listed": (out[0], out[2]), "total": (out[1], out[3])}
+
+    def screen_fallback(self):
+        """Block sums of the tile-bound refinement that the fp32 screen left
+        undecided and the double sum settled, over every batch of this context
+        so far (lm_debug_screen_fallback); 0 with LM_TILE_SCREEN=0."""
+        out = C.c_int64(0)
+        _check(lib().lm_debug_screen_fallback(self._h, C.byref(out)))
+        return int(out.value)
 
     def tail_tiles(self, f, view):
         """[tile rows, tile columns] u8: 1 where frame f's tile of tail
