@@ -175,6 +175,8 @@ BB_FRAME_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y_bottom", "y_side", "widt
 LM_JPEG_OK, LM_JPEG_NEEDS_HOST, LM_JPEG_REJECTED = 0, 1, 2
 LM_JPEG_SUBSEQ_MIN, LM_JPEG_SUBSEQ_DEFAULT, LM_JPEG_CHUNK = 4, 64, 128
 LM_BKG_MAX_SAMPLES = 65535  # include/locomouse_bkg.h: frames one lm_bkg_ctx accumulates
+# include/locomouse_calib.h
+LM_CALIB_MAX_FRAMES, LM_CALIB_MAX_RADIUS, LM_CALIB_MAX_DEGREE = 1 << 20, 4096, 3
 # include/locomouse_train.h
 LM_TRAIN_MAX_SIDE, LM_TRAIN_MAX_SAMPLES = 64, 1 << 22
 # include/locomouse_encode.h
@@ -192,6 +194,26 @@ class lm_enc_result(C.Structure):
         ("offset", C.POINTER(C.c_uint32)),
         ("size", C.POINTER(C.c_uint32)),
     ]
+
+
+class lm_calib_opts(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("radius", C.c_int32), ("min_peak", C.c_int32), ("min_area", C.c_int32),
+                ("max_stray", C.c_int32), ("reserved", C.c_int32)]
+
+
+class lm_calib_record(C.Structure):
+    _fields_ = [("peak", C.c_int32), ("px", C.c_int32), ("py", C.c_int32), ("n_above", C.c_int32), ("n_in", C.c_int32),
+                ("clipped", C.c_int32), ("S", C.c_int64), ("Sx", C.c_int64), ("Sy", C.c_int64)]
+
+
+CALIB_RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("peak", "px", "py", "n_above", "n_in", "clipped")]
+                              + [(n, "<i8") for n in ("S", "Sx", "Sy")])
+
+
+class lm_calib_fit_result(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("n_samples", C.c_int32), ("n_used", C.c_int32), ("degree", C.c_int32),
+                ("rms", C.c_double), ("max_abs_resid", C.c_double), ("lo", C.c_double), ("hi", C.c_double),
+                ("coef", C.c_double * 4)]
 
 
 class lm_train_point(C.Structure):

@@ -10,9 +10,10 @@ import subprocess
 
 import numpy as np
 
-from .abi import (BB_FRAME_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result, lm_enc_mark,
-                  lm_enc_overlay, lm_enc_result, lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_interval_stats, lm_jpeg_stats,
-                  lm_train_point, lm_train_stats, result_to_numpy)
+from .abi import (BB_FRAME_DTYPE, CALIB_RECORD_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result,
+                  lm_calib_fit_result, lm_calib_opts, lm_calib_record, lm_enc_mark, lm_enc_overlay, lm_enc_result,
+                  lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_interval_stats, lm_jpeg_stats, lm_train_point,
+                  lm_train_stats, result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -42,7 +43,7 @@ CLI_PATH = os.path.join(PKG, "bin", "LocoMouse")
 
 # translation units of liblocomouse_hip.so
 HIP_UNITS = ("lm_runtime.hip", "lm_corr.hip", "lm_bbox.hip", "lm_jpeg.hip", "lm_bkg.hip", "lm_jpeg_enc.hip",
-             "lm_train.hip")
+             "lm_train.hip", "lm_calib.hip")
 
 # include/locomouse_jpeg.h (device MJPEG decode), same library
 JPEG_EXPORTED = ("lm_jpeg_create", "lm_jpeg_destroy", "lm_jpeg_decode_device", "lm_jpeg_probe", "lm_jpeg_stream",
@@ -65,6 +66,12 @@ TRAIN_EXPORTED = ("lm_train_create", "lm_train_destroy", "lm_train_add_patches",
                   "lm_train_margins", "lm_train_stream")
 TRAIN_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTrain")
 TRANSCODE_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTranscode")
+
+# include/locomouse_calib.h (the two-view calibration map estimated from a marker video), same library
+CALIB_EXPORTED = ("lm_calib_default_opts", "lm_calib_create", "lm_calib_destroy", "lm_calib_set_background", "lm_calib_push",
+                  "lm_calib_push_device", "lm_calib_frames", "lm_calib_read", "lm_calib_reset", "lm_calib_stream",
+                  "lm_calib_fit", "lm_calib_map")
+CALIB_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseCalibrate")
 
 
 def _up_to_date(obj, cmd):
@@ -122,7 +129,7 @@ def build_host(verbose=False):
     surface (locomouse_cpp_amd/host) linked against the C-ABI library."""
     srcs = [os.path.join(HOST_DIR, f)
             for f in ("LocoMouse.cpp", "Tracks.cpp", "match2nd.cpp", "FileStorage.cpp", "Media.cpp", "Jpeg.cpp", "Debug.cpp",
-                      "Background.cpp", "JpegEncode.cpp", "Preview.cpp", "Inputs.cpp", "Train.cpp")]
+                      "Background.cpp", "JpegEncode.cpp", "Preview.cpp", "Inputs.cpp", "Train.cpp", "Calibration.cpp")]
     flags = ["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
              "-I" + HOST_DIR]
     cmd = [*flags, "-fPIC", "-shared", "-o", HOST_LIB_PATH, *srcs, "-L" + PKG, "-llocomouse_hip", "-lz",
@@ -151,6 +158,12 @@ def build_host(verbose=False):
     subprocess.check_call(cmd)
     # LocoMouseTranscode: a video written again as grey MJPEG with restart markers (the device decoder's interval path)
     cmd = [*flags, "-o", TRANSCODE_CLI_PATH, os.path.join(HOST_DIR, "TranscodeCli.cpp"), "-L" + PKG, "-llocomouse_host",
+           "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # LocoMouseCalibrate: the calibration.yml estimated from a marker video (host/Calibration.hpp)
+    cmd = [*flags, "-o", CALIB_CLI_PATH, os.path.join(HOST_DIR, "CalibrateCli.cpp"), "-L" + PKG, "-llocomouse_host",
            "-llocomouse_hip", "-Wl,-rpath,$ORIGIN/.."]
     if verbose:
         print(" ".join(cmd))
@@ -267,6 +280,23 @@ def lib():
         L.lm_train_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         L.lm_train_stream.argtypes = [C.c_void_p]
         L.lm_train_stream.restype = C.c_void_p
+        L.lm_calib_default_opts.argtypes = [C.POINTER(lm_calib_opts)]
+        L.lm_calib_default_opts.restype = None
+        L.lm_calib_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(lm_calib_opts),
+                                      C.POINTER(C.c_void_p)]
+        L.lm_calib_destroy.argtypes = [C.c_void_p]
+        L.lm_calib_set_background.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in (L.lm_calib_push, L.lm_calib_push_device):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+        L.lm_calib_frames.argtypes = [C.c_void_p]
+        L.lm_calib_frames.restype = C.c_int64
+        L.lm_calib_read.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.lm_calib_reset.argtypes = [C.c_void_p]
+        L.lm_calib_stream.argtypes = [C.c_void_p]
+        L.lm_calib_stream.restype = C.c_void_p
+        L.lm_calib_fit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(lm_calib_opts),
+                                   C.c_int32, C.c_double, C.POINTER(lm_calib_fit_result)]
+        L.lm_calib_map.argtypes = [C.POINTER(lm_calib_fit_result), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -669,6 +699,99 @@ class BackgroundEstimator:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().lm_bkg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def calib_opts(**kw):
+    """lm_calib_opts: the defaults (lm_calib_default_opts) with the given fields replaced."""
+    o = lm_calib_opts()
+    lib().lm_calib_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(lm_calib_opts._fields_):
+            raise TypeError(f"lm_calib_opts has no field {k}")
+        setattr(o, k, v)
+    return o
+
+
+def calib_fit(records, rows, cols, split_row, opts=None, degree=2, max_resid=1.5):
+    """lm_calib_fit (no GPU call) of records [n_frames, 2] (CALIB_RECORD_DTYPE: side, bottom) as a dict; a refusal
+    raises LMError with its text."""
+    rec = np.ascontiguousarray(records, dtype=CALIB_RECORD_DTYPE).reshape(-1, 2)
+    res = lm_calib_fit_result()
+    _check(lib().lm_calib_fit(rec.ctypes.data if len(rec) else (lm_calib_record * 2)(), len(rec), rows, cols, split_row,
+                              None if opts is None else C.byref(opts), degree, max_resid, C.byref(res)))
+    d = {n: getattr(res, n) for n, _ in lm_calib_fit_result._fields_ if n != "coef"}
+    d["coef"] = [res.coef[k] for k in range(degree + 1)]
+    d["raw"] = res
+    return d
+
+
+def calib_map(fit, rows, cols, split_row):
+    """lm_calib_map (no GPU call): (ind_warp_mapping [rows, cols] int32, view_boxes [2, 4] int32) of calib_fit's result."""
+    m = np.zeros((rows, cols), np.int32)
+    boxes = np.zeros((2, 4), np.int32)
+    _check(lib().lm_calib_map(C.byref(fit["raw"]), rows, cols, split_row, m.ctypes.data, boxes.ctypes.data))
+    return m, boxes
+
+
+class Calibrator:
+    """One lm_calib_ctx: the marker's record in both views (side: rows [0, split_row), bottom: the rest) of every
+    pushed frame, on one HIP device (include/locomouse_calib.h).  records() are exact integers; calib_fit and
+    calib_map turn them into the calibration map on the host."""
+
+    def __init__(self, rows, cols, split_row, max_batch=64, device=0, opts=None):
+        self._h = C.c_void_p()
+        self.opts = opts
+        _check(lib().lm_calib_create(device, rows, cols, split_row, max_batch, None if opts is None else C.byref(opts),
+                                     C.byref(self._h)))
+        self.rows, self.cols, self.split_row, self.max_batch, self.device = rows, cols, split_row, max_batch, device
+
+    def set_background(self, image):
+        """Host image [rows, cols] u8, subtracted from the frames pushed after this call."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.shape != (self.rows, self.cols):
+            raise ValueError(f"the background must be [{self.rows}, {self.cols}], not {image.shape}")
+        _check(lib().lm_calib_set_background(self._h, image.ctypes.data))
+
+    def push(self, frames):
+        """Host frames [n, rows, cols] u8."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 3 or frames.shape[1:] != (self.rows, self.cols):
+            raise ValueError(f"frames must be [n, {self.rows}, {self.cols}], not {frames.shape}")
+        _check(lib().lm_calib_push(self._h, frames.ctypes.data, self.rows * self.cols, frames.shape[0]))
+
+    def push_device(self, d_frames_ptr, pitch, n):
+        """Frames in device memory (frame i at d_frames_ptr + i * pitch); they must stay unchanged until the
+        context's stream has passed the push."""
+        _check(lib().lm_calib_push_device(self._h, C.c_void_p(d_frames_ptr), pitch, n))
+
+    @property
+    def frames(self):
+        return int(lib().lm_calib_frames(self._h))
+
+    def records(self, first=0, n=None):
+        """[n, 2] CALIB_RECORD_DTYPE (side, bottom) of frames first .. first + n - 1; waits for the stream."""
+        if n is None:
+            n = self.frames - first
+        out = np.zeros((max(n, 0), 2), dtype=CALIB_RECORD_DTYPE)
+        _check(lib().lm_calib_read(self._h, first, n, out.ctypes.data if out.size else (lm_calib_record * 2)()))
+        return out
+
+    def reset(self):
+        _check(lib().lm_calib_reset(self._h))
+
+    def stream(self):
+        return lib().lm_calib_stream(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().lm_calib_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
