@@ -155,19 +155,37 @@ inline lm_status fail(lm_status s, const std::string& m) {
   return s;
 }
 
-// Runs f, mapping the reference's exception types to lm_status codes.
+// The reference's exception types <-> lm_status codes, in both directions.
+// Runs f; the status of what it threw, its text in *msg (untouched on LM_OK).
 template <class F>
-lm_status guarded(F&& f) {
+lm_status status_of(F&& f, std::string* msg) {
   try {
     f();
     return LM_OK;
   } catch (const std::invalid_argument& e) {
-    return fail(LM_ERR_INVALID_ARGUMENT, e.what());
+    *msg = e.what();
+    return LM_ERR_INVALID_ARGUMENT;
   } catch (const HipError& e) {
-    return fail(LM_ERR_HIP, e.what());
+    *msg = e.what();
+    return LM_ERR_HIP;
   } catch (const std::exception& e) {
-    return fail(LM_ERR_RUNTIME, e.what());
+    *msg = e.what();
+    return LM_ERR_RUNTIME;
   }
+}
+// Throws what status_of turned into (s, msg); s is not LM_OK.
+[[noreturn]] inline void throw_status(lm_status s, const std::string& msg) {
+  if (s == LM_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
+  if (s == LM_ERR_HIP) throw HipError(msg);
+  throw std::runtime_error(msg);
+}
+
+// Runs f for a C-ABI call: its status, the text in lm_last_error.
+template <class F>
+lm_status guarded(F&& f) {
+  std::string msg;
+  const lm_status s = status_of(f, &msg);
+  return s == LM_OK ? LM_OK : fail(s, msg);
 }
 
 // k_minmax + k_lut (lm_kernels.hip) for slots s0 .. n-1: the per-frame

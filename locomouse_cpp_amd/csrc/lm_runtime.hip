@@ -26,6 +26,7 @@
 
 #include "locomouse_hip.h"
 #include "lm_host.h"
+#include "lm_batch_plan.h"
 #include "lm_kernels.hip"
 
 namespace {
@@ -192,7 +193,6 @@ struct lm_ctx {
   int npix = 0;
   int64_t fstride = 0;                 // device frame pitch of the staging slots
   int bb_x = 0, bb_yb = 0, bb_ys = 0;  // provided-box bottom-right corners
-  int spost_b_w = 0, spost_b_h = 0, spost_t_w = 0, spost_t_h = 0;
   int64_t ext_slot_bytes = 0, tailbin_slot_bytes = 0, dbg_slot_floats = 0;
   int64_t dbg_off[LM_NDET] = {0};
   int64_t gscratch_slot = 0;
@@ -1505,6 +1505,18 @@ void launch_attempt(lm_ctx* c, Lane& L, int attempt) {
 
 void finish_batch(lm_ctx* c, Lane& L);
 
+// What the lane holds of the batch it has just finished goes to the batch's
+// record: the pack header, the kernel timings and the dark-tile counts.
+void record_lane(const Lane& L, lm_ctx::BatchRec& rec) {
+  rec.ph = *L.h_ph.p;
+  rec.t_names = L.t_names;
+  std::copy(L.t_work, L.t_work + 4, rec.work);
+  rec.t_ms = L.t_ms;
+  rec.t_t0 = L.t_t0;
+  rec.t_t1 = L.t_t1;
+  rec.ran_lane = L.index;
+}
+
 // The batch running on lane L is complete (or failed): finish it now and
 // keep its packed results (or its error) in its queue record, so the lane
 // can take the next batch while the results wait to be collected in order.
@@ -1513,28 +1525,17 @@ void retire(lm_ctx* c, Lane& L) {
   for (auto& r : c->queue)
     if (r.lane == L.index && r.seq == L.seq) rec = &r;
   if (!rec) throw std::runtime_error("pipeline: no record of the batch running on lane " + std::to_string(L.index));
-  try {
-    finish_batch(c, L);
-    rec->ph = *L.h_ph.p;
-  } catch (const std::invalid_argument& e) {
-    rec->status = LM_ERR_INVALID_ARGUMENT;
-    rec->err = e.what();
-  } catch (const HipError& e) {
-    rec->status = LM_ERR_HIP;
-    rec->err = e.what();
-  } catch (const std::exception& e) {
-    rec->status = LM_ERR_RUNTIME;
-    rec->err = e.what();
-  }
+  rec->status = status_of([&] { finish_batch(c, L); }, &rec->err);
   if (rec->status != LM_OK) L.have_state = false;
-  rec->t_names = L.t_names;
-  std::copy(L.t_work, L.t_work + 4, rec->work);
-  rec->t_ms = L.t_ms;
-  rec->t_t0 = L.t_t0;
-  rec->t_t1 = L.t_t1;
-  rec->ran_lane = L.index;
+  record_lane(L, *rec);
   rec->lane = -1;
   L.seq = -1;
+}
+
+// Lane L continues the video after prev_frame with its own state: the one
+// predicate behind acquire_lane's preference and the batch's carry.
+bool lane_continues(const lm_ctx* c, const Lane& L, int prev_frame) {
+  return lm_bp_lane_continues(L.index, L.have_state, L.last_frame, c->last_lane, prev_frame);
 }
 
 // A free lane for the next batch: the lane that ran the previous batch when
@@ -1547,7 +1548,7 @@ Lane& acquire_lane(lm_ctx* c, int prev_frame) {
   Lane* pick = nullptr;
   for (auto& l : c->lanes) {
     if (l->seq >= 0) continue;
-    if (l->index == c->last_lane && l->have_state && l->last_frame == prev_frame) return *l;
+    if (lane_continues(c, *l, prev_frame)) return *l;
     if (!pick) pick = l.get();
   }
   if (pick) return *pick;
@@ -1567,6 +1568,151 @@ Lane& acquire_lane(lm_ctx* c, int prev_frame) {
   return *oldest;
 }
 
+// The steps of submit_batch, in its order.  A batch's arguments travel as one
+// struct; `direct`: device frames are read in place when 16-byte aligned (the
+// kernels load 16 B per lane), otherwise they are copied into the staging slots.
+struct Batch {
+  const uint8_t *frames, *prev;
+  int64_t pitch;
+  int n, first;
+  const int32_t* bb;
+  bool device_frames, direct;
+};
+
+// Reads the arguments and the context's limits and queue; changes nothing.
+void check_batch_args(const lm_ctx* c, const Batch& B) {
+  if (B.n <= 0 || B.n > c->max_batch) throw std::invalid_argument("n must be in [1, max_batch].");
+  if (B.first < 0) throw std::invalid_argument("first_frame must be >= 0.");
+  if (!B.frames) throw std::invalid_argument("frames is NULL.");
+  if (B.pitch < c->npix) throw std::invalid_argument("frame_pitch smaller than one frame.");
+  if (c->queue.size() >= 2 * c->lanes.size())
+    throw std::invalid_argument("2 x pipeline_lanes batches wait for collection: lm_detect_collect first.");
+}
+
+// Slot table and frame pointers.  Reads the geometry, the provided box, the
+// caller's corners and the context's last_bb (lm_bp_slots); writes the lane's
+// h_slots and h_frame_ptr and returns the corners the next batch inherits in
+// new_last_bb.  Throws before anything reaches the stream.
+void fill_slots(const lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M, int (&new_last_bb)[3]) {
+  const int box[3] = {c->bb_x, c->bb_yb, c->bb_ys};
+  lm_bp_slots(B.n, B.first, M, c->geo, box, c->K.gray_lut_on != 0, B.bb, c->last_bb, L.h_slots.p, new_last_bb);
+  L.h_frame_ptr.p[0] = L.halo.p;
+  for (int s = 1; s <= B.n; ++s)
+    L.h_frame_ptr.p[s] = B.direct ? B.frames + (int64_t)(s - 1) * B.pitch : L.frames.p + (int64_t)s * c->fstride;
+}
+
+// Staging copies.  Host frames (and a host halo frame) are the only runtime
+// copies from the caller's memory; the stream is drained after them, so the
+// caller may reuse its buffer once submit_batch returns (see k_prep / k_out
+// for why the stream otherwise holds only kernels).  Reads the caller's
+// frames; writes the lane's staging slots and halo on its stream.
+void stage_inputs(const lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M) {
+  hipStream_t st = L.stream;
+  const int64_t fstride = c->fstride;
+  const hipMemcpyKind kind = B.device_frames ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (!B.direct)  // one 2-D transfer for the batch (host frames: DMA from page-locked buffers, e.g. lm_host_alloc)
+    HIPCHK(hipMemcpy2DAsync(L.frames.p + fstride, (size_t)fstride, B.frames, (size_t)B.pitch, (size_t)c->npix,
+                            (size_t)B.n, kind, st));
+  if (M.given_halo && B.device_frames && ((uintptr_t)B.prev & 15) == 0)
+    k_out<<<64, 256, 0, st>>>(L.zero_ph.p, L.h_ph.d, nullptr, nullptr, 0, nullptr, B.prev, nullptr, 0, L.halo.p, c->npix);
+  else if (M.given_halo)
+    HIPCHK(hipMemcpyAsync(L.halo.p, B.prev, (size_t)c->npix, kind, st));
+  if (!B.device_frames) HIPCHK(hipStreamSynchronize(st));
+}
+
+// Pipelined halo hand-off (every batch of a multi-lane context).  Reads the
+// batch's last frame, the previous lane's events and, on a hand-off, the
+// frame the previous batch left; writes handoff[nsub & 1], the lane's halo
+// and its events ev_snap and ev_consumed.
+void hand_off_halo(lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M) {
+  hipStream_t st = L.stream;
+  const int64_t fstride = c->fstride;
+  const uint8_t* last = B.direct ? B.frames + (int64_t)(B.n - 1) * B.pitch : L.frames.p + (int64_t)B.n * fstride;
+  // handoff[k & 1] was last read by batch k - 1 (it took batch k - 2's frame from there)
+  if (c->last_lane >= 0) HIPCHK(hipStreamWaitEvent(st, c->lanes[c->last_lane]->ev_consumed, 0));
+  HIPCHK(hipMemcpyAsync(c->handoff.p + (c->nsub & 1) * fstride, last, (size_t)c->npix, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipEventRecord(L.ev_snap, st));
+  if (M.handoff) {
+    HIPCHK(hipStreamWaitEvent(st, c->lanes[c->last_lane]->ev_snap, 0));
+    HIPCHK(hipMemcpyAsync(L.halo.p, c->handoff.p + ((c->nsub - 1) & 1) * fstride, (size_t)c->npix,
+                          hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHK(hipEventRecord(L.ev_consumed, st));
+}
+
+// Source-map refresh: k_ingest's map of a view is rebuilt when every processed
+// slot has its crop at one position (lm_bp_uniform_crop) that the lane's map
+// does not hold.  Reads h_slots and skey_h; writes smap, sbkg, skey, skey_h.
+void refresh_source_map(const lm_ctx* c, Lane& L, int n, int s_proc0) {
+  for (int v = 0; v < 2; ++v) {
+    const auto at = lm_bp_uniform_crop(L.h_slots.p, n, s_proc0, v);
+    if (!at || (L.skey_h[2 * v] == at->first && L.skey_h[2 * v + 1] == at->second)) continue;
+    const int64_t nv = (int64_t)c->K.ext_h[v] * c->K.ext_w[v] / LM_INGEST_VEC;
+    k_srcmap<<<(unsigned)((nv + 255) / 256), 256, 0, L.stream>>>(c->dK.p, c->cal.p, c->bkg.p, v, at->first, at->second,
+                                                                L.smap.p, L.sbkg.p, L.skey.p);
+    HIPCHK(hipGetLastError());
+    L.skey_h[2 * v] = at->first;
+    L.skey_h[2 * v + 1] = at->second;
+  }
+}
+
+// Pending and launch.  Fills the lane's Pending from the mode and the lane's
+// parity, takes a result buffer and enqueues the batch (launch_attempt, the
+// dark-tile counters' copy under debug bit 1, ev_done).  On failure its kernels
+// may be enqueued already: the lane and the pack are free once the stream drained.
+void launch_pending(lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M) {
+  Lane::Pending& P = L.pend;
+  P.on = true;
+  P.n = B.n;
+  P.first = B.first;
+  P.s_lut0 = M.s_lut0;
+  P.s_proc0 = M.s_proc0;
+  P.plan = corr_plan_for(c);
+  P.cur = L.parity;
+  P.prv = L.last_parity;
+  P.carry = M.carry;
+  P.last_n = M.carry ? L.last_n : 0;
+  P.pack = c->take_pack((size_t)L.arena[P.cur].pack_cap);
+  try {
+    launch_attempt(c, L, 0);
+    L.h_cnt_valid = (c->debug & 2) && L.dark_cnt.p;
+    if (L.h_cnt_valid)
+      HIPCHK(hipMemcpyAsync(L.h_cnt.p, L.dark_cnt.p, 4 * LM_TL_NC * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(hipEventRecord(L.ev_done, L.stream));
+  } catch (...) {
+    (void)hipStreamSynchronize(L.stream);
+    (void)hipGetLastError();
+    c->drop_pack(P.pack);
+    P.on = false;
+    throw;
+  }
+}
+
+// Advance, only now that the launch succeeded: the video position and the lane's
+// carry state move past the batch and its record joins the queue.  (A batch that
+// fails at collection clears the lane's state; other lanes only need its pixels.)
+void advance_position(lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M, const int (&new_last_bb)[3]) {
+  c->have_state = true;
+  c->last_frame = B.first + B.n - 1;
+  for (int k = 0; k < 3; ++k) c->last_bb[k] = new_last_bb[k];
+  c->last_lane = L.index;
+  L.seq = c->nsub;
+  lm_ctx::BatchRec rec;
+  rec.seq = c->nsub;
+  rec.lane = L.index;
+  rec.pack = L.pend.pack;
+  rec.first = B.first;
+  rec.n = B.n;
+  rec.slots = B.n + 1 - M.s_proc0;
+  c->queue.push_back(std::move(rec));
+  ++c->nsub;
+  L.have_state = true;
+  L.last_frame = B.first + B.n - 1;
+  L.last_n = B.n;
+  L.last_parity = L.pend.cur;
+  L.parity = 1 - L.pend.cur;
+}
+
 // Submit frames [first, first + n) to a free lane (acquire_lane).  Host
 // frames are copied to the lane's staging slots before this returns; device
 // frames are read in place while the batch runs.  At most 2 x lanes batches
@@ -1578,234 +1724,114 @@ Lane& acquire_lane(lm_ctx* c, int prev_frame) {
 //    start (event ev_snap); batch k + 1 copies it into its own halo (event
 //    ev_consumed) and runs it as a 1-frame halo (its candidates recomputed),
 //    so the two batches' kernels never wait for each other.
+// What reaches the stream does so in the order of the steps below.
 void submit_batch(lm_ctx* c, const uint8_t* frames, int64_t pitch, int n, int first, const uint8_t* prev,
                   const int32_t* bb, bool device_frames) {
-  if (n <= 0 || n > c->max_batch) throw std::invalid_argument("n must be in [1, max_batch].");
-  if (first < 0) throw std::invalid_argument("first_frame must be >= 0.");
-  if (!frames) throw std::invalid_argument("frames is NULL.");
-  if (pitch < c->npix) throw std::invalid_argument("frame_pitch smaller than one frame.");
-  if (c->queue.size() >= 2 * c->lanes.size())
-    throw std::invalid_argument("2 x pipeline_lanes batches wait for collection: lm_detect_collect first.");
+  const Batch B{frames, prev, pitch, n, first, bb, device_frames,
+                device_frames && ((((uintptr_t)frames | (uintptr_t)pitch) & 15) == 0)};
+  check_batch_args(c, B);
   HIPCHK(hipSetDevice(c->device));
+  // mode (lm_batch_plan.h): the lane is picked between "does the batch
+  // continue the previous one" and "does its lane carry"
   const bool pipelined = c->lanes.size() > 1;
-  const bool given_halo = prev != nullptr && first > 0;
-  const bool cont = !given_halo && first > 0;
-  if (cont && !(c->have_state && c->last_frame == first - 1))
-    throw std::invalid_argument("frame first_frame-1 was not processed by this context: pass prev_frame (shard start).");
+  const bool cont = lm_bp_continues(first, prev != nullptr, c->have_state, c->last_frame);
   Lane& L = acquire_lane(c, cont ? first - 1 : -2);
-  const bool carry = cont && c->last_lane == L.index && L.have_state && L.last_frame == first - 1;
-  const bool handoff = cont && !carry;
-  if (handoff && !pipelined)
-    throw std::invalid_argument("the previous batch failed: pass prev_frame to continue from frame first_frame.");
-  const bool halo = given_halo || handoff;
-  const lm_geometry& g = c->geo;
-  const LmConst& K = c->K;
-  const int64_t fstride = c->fstride;
-  hipStream_t st = L.stream;
-
-  // Device frames are read in place when 16-byte aligned (the kernels load
-  // 16 B per lane); otherwise they are first copied into the staging slots.
-  const bool direct = device_frames && ((((uintptr_t)frames | (uintptr_t)pitch) & 15) == 0);
-  // ---- slots: frame pointers and crop rectangles (cropBoundingBox :1420-1470)
-  const int s_lut0 = first > 0 ? 0 : 1, s_proc0 = halo ? 0 : 1;
-  int new_last_bb[3] = {c->bb_x, c->bb_yb, c->bb_ys};
-  for (int s = 0; s <= n; ++s) {
-    LmSlot& S = L.h_slots.p[s];
-    std::memset(&S, 0, sizeof(S));
-    const int gframe = first - 1 + s;
-    S.frame = gframe;
-    S.active = s >= s_lut0;
-    if (s == 0) L.h_frame_ptr.p[0] = L.halo.p;
-    else L.h_frame_ptr.p[s] = direct ? frames + (int64_t)(s - 1) * pitch : L.frames.p + (int64_t)s * fstride;
-    if (s < s_lut0) continue;
-    const int bi = given_halo ? s : s - 1;  // index into bb[]
-    int bx = c->bb_x, byb = c->bb_yb, bys = c->bb_ys;
-    if (bb && (s > 0 || given_halo)) {
-      bx = bb[3 * bi];
-      byb = bb[3 * bi + 1];
-      bys = bb[3 * bi + 2];
-    } else if (s == 0 && cont) {  // the previous batch's last frame
-      bx = c->last_bb[0];
-      byb = c->last_bb[1];
-      bys = c->last_bb[2];
-    }
-    if (s == n) {
-      new_last_bb[0] = bx;
-      new_last_bb[1] = byb;
-      new_last_bb[2] = bys;
-    }
-    S.crop_x[0] = (int)((unsigned)(bx + g.pad_pre_cols) - (unsigned)(g.bb_bottom_mouse_pad.width - g.spost_b_w) + 1u);
-    S.crop_y[0] = (int)((unsigned)(byb + g.pad_pre_rows) - (unsigned)(g.bb_bottom_mouse_pad.height - g.spost_b_h) + 1u);
-    S.crop_x[1] = (int)((unsigned)(g.pad_pre_cols + bx) - (unsigned)(g.bb_side_mouse_pad.width - g.spost_t_w) + 1u);
-    S.crop_y[1] = (int)((unsigned)(g.pad_pre_rows + bys) - (unsigned)(g.bb_side_mouse_pad.height - g.spost_t_h) + 1u);
-    const int w[2] = {g.bb_bottom_mouse_pad.width, g.bb_side_mouse_pad.width};
-    const int h[2] = {g.bb_bottom_mouse_pad.height, g.bb_side_mouse_pad.height};
-    if (s >= s_proc0)
-      for (int v = 0; v < 2; ++v)
-        if (S.crop_x[v] < 0 || S.crop_y[v] < 0 || S.crop_x[v] + w[v] > g.ipad_cols || S.crop_y[v] + h[v] > g.ipad_rows)
-          throw std::runtime_error(std::string("ROI out of image bounds: ") + (v ? "BB_SIDE_MOUSE_PAD" : "BB_BOTTOM_MOUSE_PAD"));
-    if (K.gray_lut_on) {  // the in-place LUT must stay inside I_UNPAD (see locomouse_hip.h)
-      const int ux = S.crop_x[0] + g.spre_b_w, uy = S.crop_y[0] + g.spre_b_h;
-      if (ux < g.pad_pre_cols || uy < g.pad_pre_rows || ux + g.bb_bottom_mouse.width > g.pad_pre_cols + g.n_cols ||
-          uy + g.bb_bottom_mouse.height > g.pad_pre_rows + g.n_rows)
-        throw std::invalid_argument("transform_gray_values: frame " + std::to_string(S.frame) +
-                                    ": the bottom crop leaves the corrected image, so the in-place LUT would reach "
-                                    "I_PAD's zero padding (not supported).");
-    }
-  }
-
-  // ---- inputs.  Host frames (and a host halo frame) are the only runtime
-  // copies from the caller's memory; the stream is drained after them, so
-  // the caller may reuse its buffer once this returns (see k_prep / k_out for
-  // why the stream otherwise holds only kernels).
-  if (!device_frames) {
-    // one 2-D transfer for the batch (DMA from page-locked buffers, e.g. lm_host_alloc)
-    HIPCHK(hipMemcpy2DAsync(L.frames.p + fstride, (size_t)fstride, frames, (size_t)pitch, (size_t)c->npix, (size_t)n,
-                            hipMemcpyHostToDevice, st));
-    if (given_halo) HIPCHK(hipMemcpyAsync(L.halo.p, prev, c->npix, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-  } else {
-    if (!direct)
-      HIPCHK(hipMemcpy2DAsync(L.frames.p + fstride, (size_t)fstride, frames, (size_t)pitch, (size_t)c->npix, (size_t)n,
-                              hipMemcpyDeviceToDevice, st));
-    if (given_halo && ((uintptr_t)prev & 15) == 0)
-      k_out<<<64, 256, 0, st>>>(L.zero_ph.p, L.h_ph.d, nullptr, nullptr, 0, nullptr, prev, nullptr, 0, L.halo.p,
-                                c->npix);
-    else if (given_halo)
-      HIPCHK(hipMemcpyAsync(L.halo.p, prev, (size_t)c->npix, hipMemcpyDeviceToDevice, st));
-  }
-  // ---- pipelined halo hand-off (every batch of a multi-lane context)
-  if (pipelined) {
-    const uint8_t* last = direct ? frames + (int64_t)(n - 1) * pitch : L.frames.p + (int64_t)n * fstride;
-    // handoff[k & 1] was last read by batch k - 1 (it took batch k - 2's frame from there)
-    if (c->last_lane >= 0) HIPCHK(hipStreamWaitEvent(st, c->lanes[c->last_lane]->ev_consumed, 0));
-    HIPCHK(hipMemcpyAsync(c->handoff.p + (c->nsub & 1) * fstride, last, (size_t)c->npix, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipEventRecord(L.ev_snap, st));
-    if (handoff) {
-      HIPCHK(hipStreamWaitEvent(st, c->lanes[c->last_lane]->ev_snap, 0));
-      HIPCHK(hipMemcpyAsync(L.halo.p, c->handoff.p + ((c->nsub - 1) & 1) * fstride, (size_t)c->npix,
-                            hipMemcpyDeviceToDevice, st));
-    }
-    HIPCHK(hipEventRecord(L.ev_consumed, st));
-  }
+  const LmBatchMode M = lm_bp_mode(first, prev != nullptr, cont, lane_continues(c, L, first - 1), pipelined);
+  int new_last_bb[3];
+  fill_slots(c, L, B, M, new_last_bb);
+  stage_inputs(c, L, B, M);
+  if (pipelined) hand_off_halo(c, L, B, M);
   if (!L.gscratch.p) L.gscratch.alloc((size_t)c->gscratch_slot * LM_GLOB_BLOCKS);  // one region per block of the <true> launches
-  // k_ingest's source map: rebuilt for a view when every processed slot has
-  // its crop at one position that the lane's map does not hold
-  for (int v = 0; v < 2; ++v) {
-    const LmSlot& S0 = L.h_slots.p[s_proc0];
-    bool uni = true;
-    for (int s = s_proc0 + 1; s <= n && uni; ++s)
-      uni = L.h_slots.p[s].crop_x[v] == S0.crop_x[v] && L.h_slots.p[s].crop_y[v] == S0.crop_y[v];
-    if (uni && (L.skey_h[2 * v] != S0.crop_x[v] || L.skey_h[2 * v + 1] != S0.crop_y[v])) {
-      const int64_t nv = (int64_t)K.ext_h[v] * K.ext_w[v] / LM_INGEST_VEC;
-      k_srcmap<<<(unsigned)((nv + 255) / 256), 256, 0, st>>>(c->dK.p, c->cal.p, c->bkg.p, v, S0.crop_x[v], S0.crop_y[v],
-                                                            L.smap.p, L.sbkg.p, L.skey.p);
-      HIPCHK(hipGetLastError());
-      L.skey_h[2 * v] = S0.crop_x[v];
-      L.skey_h[2 * v + 1] = S0.crop_y[v];
-    }
-  }
+  refresh_source_map(c, L, n, M.s_proc0);
+  launch_pending(c, L, B, M);
+  advance_position(c, L, B, M, new_last_bb);
+}
 
-  Lane::Pending& P = L.pend;
-  P.on = true;
-  P.n = n;
-  P.first = first;
-  P.s_lut0 = s_lut0;
-  P.s_proc0 = s_proc0;
-  P.plan = corr_plan_for(c);
-  P.cur = L.parity;
-  P.prv = L.last_parity;
-  P.carry = carry;
-  P.last_n = carry ? L.last_n : 0;
-  P.pack = c->take_pack((size_t)L.arena[P.cur].pack_cap);
-  try {
-    launch_attempt(c, L, 0);
-    L.h_cnt_valid = (c->debug & 2) && L.dark_cnt.p;
-    if (L.h_cnt_valid)
-      HIPCHK(hipMemcpyAsync(L.h_cnt.p, L.dark_cnt.p, 4 * LM_TL_NC * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(L.ev_done, st));
-  } catch (...) {
-    // kernels of this batch may already be enqueued: the lane (and the pack
-    // k_out writes into) is free only once its stream has drained
-    (void)hipStreamSynchronize(st);
-    (void)hipGetLastError();
-    c->drop_pack(P.pack);
-    P.on = false;
-    throw;
+// The steps of finish_batch.
+// Device-error decode: throws for the error bits err of the finished attempt
+// (the text of the reference's assertion where it has one).  Reads the lane's
+// error record for bit 2 (the velocity criterion's match box); LM_DUMP_DIR
+// dumps that slot first; debug bit 2 reports bit 2 and keeps going.
+void check_device_errors(lm_ctx* c, Lane& L, int err) {
+  const int first = L.pend.first;
+  const int e = (c->debug & 4) ? (err & ~4) : err;
+  const int32_t* d = L.h_err.p;
+  if (err & 4) COPY_SYNC(L.h_err.p, L.err.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, L.stream);
+  if ((c->debug & 4) && (err & 4))
+    fprintf(stderr, "[lm debug] vel box error frame %d tag %x box (%d,%d,%d,%d)\n", first - 1 + (d[2] >> 16), d[2],
+            d[3], d[4], d[5], d[6]);
+  if (e & 4) {
+    const int tag = d[2], slot = tag >> 16;
+    if (const char* dir = getenv("LM_DUMP_DIR")) dump_slot(c, L, dir, first - 1 + slot, slot, (tag >> 12) & 1);
+    char buf[256];
+    snprintf(buf, sizeof buf, " [frame %d, %s %s candidate %d: box (%d,%d,%d,%d) in crop %dx%d]",
+             first - 1 + slot, (tag >> 12 & 1) ? "snout" : "paw", (tag & 0x800) ? "side" : "bottom", tag & 0x7FF,
+             d[3], d[4], d[5], d[6], d[7], d[8]);
+    throw std::runtime_error(std::string("checkVelCriterion: match box outside the padded crop (cv::Mat ROI "
+                                         "assertion).") + buf);
   }
+  if (e & 16) throw std::runtime_error("P22D::add_side_candidate_safe: CV_Assert(S >= 0) failed.");
+  if (e & 8) throw std::runtime_error("candidate list exceeds the k_post scratch capacity.");
+  if (e & 32) throw std::runtime_error("candidate staging overflow.");
+  if (e & LM_DEVERR_CORR_DIR) throw std::runtime_error("correlation: a launch group's listed waves exceed its grid.");
+  if (e) throw std::runtime_error("device error flags " + std::to_string(e));
+}
 
-  // the video position and the lane's carry state advance now; a batch that
-  // fails at collection clears the lane's state (a later batch on another
-  // lane only needs this batch's pixels)
-  c->have_state = true;
-  c->last_frame = first + n - 1;
-  for (int k = 0; k < 3; ++k) c->last_bb[k] = new_last_bb[k];
-  c->last_lane = L.index;
-  L.seq = c->nsub;
-  lm_ctx::BatchRec rec;
-  rec.seq = c->nsub;
-  rec.lane = L.index;
-  rec.pack = P.pack;
-  rec.first = first;
-  rec.n = n;
-  rec.slots = n + 1 - s_proc0;
-  c->queue.push_back(std::move(rec));
-  ++c->nsub;
-  L.have_state = true;
-  L.last_frame = first + n - 1;
-  L.last_n = n;
-  L.last_parity = P.cur;
-  L.parity = 1 - P.cur;
+// Arena growth after an overflow: the arenas that overflowed (overflow bit 1)
+// to 1.25 x what the attempt used, the pack to 1.25 x its bytes.  The lane's
+// graphs hold the old addresses and are dropped first.
+void grow_arena(const lm_ctx* c, Lane& L, Arena& A, const LmPackHdr& ph) {
+  L.drop_graphs();
+  if (ph.overflow & 2) {
+    int ncap[AR_COUNT];
+    for (int k = 0; k < AR_COUNT; ++k) ncap[k] = std::max(A.cap[k], (int)(ph.used[k] * 1.25) + 1024);
+    A.alloc(ncap, c->nslots);
+  }
+  A.alloc_pack(ph.bytes + ph.bytes / 4);
+}
+
+// Pack re-delivery: the packed results (lm_batch_result layout) are in the
+// batch's pinned buffer HP unless they outgrew it; then it grows and k_out
+// copies them (and the halo) again.
+void redeliver_pack(const lm_ctx* c, Lane& L, Arena& A, HostBuf<uint8_t>& HP, const LmPackHdr& ph) {
+  if ((int64_t)HP.n >= ph.bytes) return;
+  HP.alloc((size_t)(ph.bytes + ph.bytes / 4));
+  k_out<<<128, 256, 0, L.stream>>>(A.ph.p, L.h_ph.d, A.pack.p, HP.d, (int64_t)HP.n, nullptr, nullptr, L.frame_ptr.p,
+                                   L.pend.n, L.halo.p, c->npix);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(L.stream));
+}
+
+// Diagnostics (debug bit 3): a second, synchronous copy of the pack must equal
+// the one k_out delivered to HP; reports the first and last differing byte.
+void compare_pack_copy(const Lane& L, const Arena& A, const HostBuf<uint8_t>& HP, const LmPackHdr& ph) {
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<uint8_t> chk((size_t)ph.bytes);
+  HIPCHK(hipMemcpy(chk.data(), A.pack.p, (size_t)ph.bytes, hipMemcpyDeviceToHost));
+  const int64_t i = std::mismatch(chk.begin(), chk.end(), HP.p).first - chk.begin();
+  if (i == ph.bytes) return;
+  int64_t j = ph.bytes - 1;
+  while (j > i && chk[j] == HP.p[j]) --j;
+  fprintf(stderr, "[lm debug] D2H pack mismatch frames %d..%d: bytes [%ld, %ld] of %ld differ\n", L.pend.first,
+          L.pend.first + L.pend.n - 1, (long)i, (long)j, (long)ph.bytes);
 }
 
 // Wait for the lane's batch and rerun it while its result arena overflows;
 // its packed results are then in the batch's result buffer.
 void finish_batch(lm_ctx* c, Lane& L) {
   Lane::Pending& P = L.pend;
-  hipStream_t st = L.stream;
-  const int n = P.n, first = P.first;
   HIPCHK(hipSetDevice(c->device));
+  Arena& A = L.arena[P.cur];
   for (int attempt = 0;; ++attempt) {
     if (attempt > 0) {
       launch_attempt(c, L, attempt);
       L.h_cnt_valid = false;  // (the counters of the rerun: read synchronously)
     }
-    HIPCHK(hipStreamSynchronize(st));
-    Arena& A = L.arena[P.cur];
-    const LmPackHdr& ph = *L.h_ph.p;
-    const int e = (c->debug & 4) ? (ph.err & ~4) : ph.err;  // debug bit 2: report but keep going
-    if ((c->debug & 4) && (ph.err & 4)) {
-      COPY_SYNC(L.h_err.p, L.err.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-      const int32_t* d = L.h_err.p;
-      fprintf(stderr, "[lm debug] vel box error frame %d tag %x box (%d,%d,%d,%d)\n", first - 1 + (d[2] >> 16), d[2],
-              d[3], d[4], d[5], d[6]);
-    }
-    if (e & 4) {
-      COPY_SYNC(L.h_err.p, L.err.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-      const int32_t* d = L.h_err.p;
-      const int tag = d[2], slot = tag >> 16;
-      if (const char* dir = getenv("LM_DUMP_DIR")) dump_slot(c, L, dir, first - 1 + slot, slot, (tag >> 12) & 1);
-      char buf[256];
-      snprintf(buf, sizeof buf, " [frame %d, %s %s candidate %d: box (%d,%d,%d,%d) in crop %dx%d]",
-               first - 1 + slot, (tag >> 12 & 1) ? "snout" : "paw", (tag & 0x800) ? "side" : "bottom", tag & 0x7FF,
-               d[3], d[4], d[5], d[6], d[7], d[8]);
-      throw std::runtime_error(std::string("checkVelCriterion: match box outside the padded crop (cv::Mat ROI "
-                                           "assertion).") + buf);
-    }
-    if (e & 16) throw std::runtime_error("P22D::add_side_candidate_safe: CV_Assert(S >= 0) failed.");
-    if (e & 8) throw std::runtime_error("candidate list exceeds the k_post scratch capacity.");
-    if (e & 32) throw std::runtime_error("candidate staging overflow.");
-    if (e & LM_DEVERR_CORR_DIR) throw std::runtime_error("correlation: a launch group's listed waves exceed its grid.");
-    if (e) throw std::runtime_error("device error flags " + std::to_string(e));
-    if (!ph.overflow) break;
+    HIPCHK(hipStreamSynchronize(L.stream));
+    check_device_errors(c, L, L.h_ph.p->err);
+    if (!L.h_ph.p->overflow) break;
     if (attempt >= 3) throw std::runtime_error("result arena overflow persists.");
-    L.drop_graphs();  // arena / pack buffers are reallocated below
-    if (ph.overflow & 2) {
-      int ncap[AR_COUNT];
-      for (int k = 0; k < AR_COUNT; ++k) ncap[k] = std::max(A.cap[k], (int)(ph.used[k] * 1.25) + 1024);
-      A.alloc(ncap, c->nslots);
-    }
-    A.alloc_pack(ph.bytes + ph.bytes / 4);
+    grow_arena(c, L, A, *L.h_ph.p);
   }
   if (c->debug & 2) {
     Timer::collect(c, L);
@@ -1813,39 +1839,16 @@ void finish_batch(lm_ctx* c, Lane& L) {
     L.t_ev.clear();
     for (int k = 0; k < 4; ++k) L.t_work[k] = -1;
   }
-  if (c->kprof_on) kprof_report(c, L, n);
-
-  // ---- the packed results (lm_batch_result layout) are in the batch's
-  // buffer unless they outgrew it: then grow it and let k_out copy them (and
-  // the halo) again
-  Arena& A = L.arena[P.cur];
+  if (c->kprof_on) kprof_report(c, L, P.n);
   const LmPackHdr ph = *L.h_ph.p;
   HostBuf<uint8_t>& HP = *c->packs[P.pack];
-  if ((int64_t)HP.n < ph.bytes) {
-    HP.alloc((size_t)(ph.bytes + ph.bytes / 4));
-    k_out<<<128, 256, 0, st>>>(A.ph.p, L.h_ph.d, A.pack.p, HP.d, (int64_t)HP.n, nullptr, nullptr, L.frame_ptr.p, n,
-                               L.halo.p, c->npix);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-  }
+  redeliver_pack(c, L, A, HP, ph);
   if (guard_mode()) {
     HIPCHK(hipDeviceSynchronize());
     guard_check_all();
   }
-  if (c->debug & 8) {  // diagnostics: a second, synchronous copy of the pack must equal the async one
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<uint8_t> chk((size_t)ph.bytes);
-    HIPCHK(hipMemcpy(chk.data(), A.pack.p, (size_t)ph.bytes, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < ph.bytes; ++i)
-      if (chk[i] != HP.p[i]) {
-        int64_t j = ph.bytes - 1;
-        while (j > i && chk[j] == HP.p[j]) --j;
-        fprintf(stderr, "[lm debug] D2H pack mismatch frames %d..%d: bytes [%ld, %ld] of %ld differ\n", first,
-                first + n - 1, (long)i, (long)j, (long)ph.bytes);
-        break;
-      }
-  }
-  L.batch_n = n;
+  if (c->debug & 8) compare_pack_copy(L, A, HP, ph);
+  L.batch_n = P.n;
   L.batch_s0 = P.s_proc0;
   L.done_seq = L.seq;
   P.on = false;
@@ -1885,7 +1888,6 @@ void collect_batch(lm_ctx* c, lm_batch_result* out) {
   c->delivered.pack = -1;
   if (rec.lane >= 0) {  // still on its lane: finish it there
     Lane& L = *c->lanes[rec.lane];
-    rec.ran_lane = L.index;
     try {
       finish_batch(c, L);
     } catch (...) {
@@ -1896,18 +1898,11 @@ void collect_batch(lm_ctx* c, lm_batch_result* out) {
       throw;
     }
     L.seq = -1;
-    rec.t_names = L.t_names;
-    std::copy(L.t_work, L.t_work + 4, rec.work);
-    rec.t_ms = L.t_ms;
-    rec.t_t0 = L.t_t0;
-    rec.t_t1 = L.t_t1;
-    rec.ph = *L.h_ph.p;
+    record_lane(L, rec);
   }
   if (rec.status != LM_OK) {
     c->drop_pack(rec.pack);
-    if (rec.status == LM_ERR_INVALID_ARGUMENT) throw std::invalid_argument(rec.err);
-    if (rec.status == LM_ERR_HIP) throw HipError(rec.err);
-    throw std::runtime_error(rec.err);
+    throw_status(rec.status, rec.err);
   }
   c->delivered = std::move(rec);
   fill_result(out, c->packs[c->delivered.pack]->p, c->delivered.n, c->delivered.first, c->delivered.ph);
@@ -2058,16 +2053,27 @@ LM_API lm_status lm_ctx_set_debug(lm_ctx* ctx, int32_t flags) {
   });
 }
 
-LM_API int32_t lm_debug_kernel_spans(lm_ctx* ctx, const char** names, double* t0, double* t1, int32_t cap) {
+// The delivered batch's timed kernels: up to cap names, durations and spans
+// into the arrays that are not null; returns how many there are.
+static int32_t kernel_timings(const lm_ctx* ctx, const char** names, double* ms, double* t0, double* t1, int32_t cap) {
   if (!ctx) return 0;
-  const lm_ctx::BatchRec& L = ctx->delivered;
-  const int32_t n = (int32_t)L.t_names.size();
+  const lm_ctx::BatchRec& D = ctx->delivered;
+  const int32_t n = (int32_t)D.t_names.size();
   for (int32_t i = 0; i < n && i < cap; ++i) {
-    if (names) names[i] = L.t_names[i];
-    if (t0) t0[i] = L.t_t0[i];
-    if (t1) t1[i] = L.t_t1[i];
+    if (names) names[i] = D.t_names[i];
+    if (ms) ms[i] = D.t_ms[i];
+    if (t0) t0[i] = D.t_t0[i];
+    if (t1) t1[i] = D.t_t1[i];
   }
   return n;
+}
+
+LM_API int32_t lm_debug_kernel_spans(lm_ctx* ctx, const char** names, double* t0, double* t1, int32_t cap) {
+  return kernel_timings(ctx, names, nullptr, t0, t1, cap);
+}
+
+LM_API int32_t lm_debug_kernel_times(lm_ctx* ctx, const char** names, double* ms, int32_t cap) {
+  return kernel_timings(ctx, names, ms, nullptr, nullptr, cap);
 }
 
 LM_API lm_status lm_debug_corr_work(const lm_ctx* ctx, int32_t* out) {
@@ -2095,21 +2101,37 @@ const Lane* delivered_lane(const lm_ctx* ctx) {
 const char* kLaneReused =
     "the collected batch's lane already runs a newer batch, so its debug data is gone: collect it before submitting "
     "more batches (or use one pipeline lane)";
+
+// What the lm_debug_* readers of the delivered batch's device data share,
+// after their null check and "skip is off" answers: the lane must still hold
+// that batch; bad(L) is the reader's own argument check against it (what is
+// wrong, or null); then read(L, fetch) runs on the context's device, where
+// fetch(dst, src, bytes) is a waited-for copy out of the lane's buffers.
+template <class Bad, class Read>
+lm_status read_delivered(lm_ctx* ctx, Bad&& bad, Read&& read) {
+  const Lane* L = delivered_lane(ctx);
+  if (!L) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
+  if (const char* what = bad(*L)) return fail(LM_ERR_INVALID_ARGUMENT, what);
+  return guarded([&] {
+    HIPCHK(hipSetDevice(ctx->device));
+    read(*L, [&](void* dst, const void* src, size_t bytes) {
+      COPY_SYNC(dst, src, bytes, hipMemcpyDeviceToHost, L->stream);
+    });
+  });
+}
+const char* no_check(const Lane&) { return nullptr; }
 }  // namespace
 
 LM_API lm_status lm_debug_scores(lm_ctx* ctx, int32_t f, int32_t det, float* out, int32_t rows, int32_t cols) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  if (!(ctx->debug & 1) || !L.dbg.p) return fail(LM_ERR_INVALID_ARGUMENT, "debug scores not enabled");
-  if (f < 0 || f >= L.batch_n || det < 0 || det >= LM_NDET) return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
-  const LmDet& D = ctx->K.det[det];
-  if (rows != D.oh || cols != D.ow) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
-    COPY_SYNC(out, L.dbg.p + (int64_t)(f + 1) * ctx->dbg_slot_floats + ctx->dbg_off[det], sizeof(float) * rows * cols,
-              hipMemcpyDeviceToHost, L.stream);
+  const auto bad = [&](const Lane& L) -> const char* {
+    if (!(ctx->debug & 1) || !L.dbg.p) return "debug scores not enabled";
+    if (f < 0 || f >= L.batch_n || det < 0 || det >= LM_NDET) return "index out of range";
+    if (rows != ctx->K.det[det].oh || cols != ctx->K.det[det].ow) return "shape mismatch";
+    return nullptr;
+  };
+  return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
+    fetch(out, L.dbg.p + (int64_t)(f + 1) * ctx->dbg_slot_floats + ctx->dbg_off[det], sizeof(float) * rows * cols);
   });
 }
 
@@ -2117,13 +2139,9 @@ LM_API lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
   for (int k = 0; k < 4; ++k) out[k] = -1;
   if (!ctx->tailskip_on) return LM_OK;
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
+  return read_delivered(ctx, no_check, [&](const Lane& L, auto fetch) {
     int32_t h[2 * LM_TL_NC];
-    COPY_SYNC(h, L.tail_cnt.p, sizeof(h), hipMemcpyDeviceToHost, L.stream);
+    fetch(h, L.tail_cnt.p, sizeof(h));
     for (int t = 0; t < 2; ++t) {
       out[2 * t] = std::accumulate(h + t * LM_TL_NC, h + (t + 1) * LM_TL_NC, 0);
       out[2 * t + 1] = ctx->delivered.slots * ctx->K.tt_tx[t] * ctx->K.tt_ty[t];
@@ -2147,15 +2165,13 @@ LM_API lm_status lm_debug_screen_fallback(lm_ctx* ctx, int64_t* out) {
 LM_API lm_status lm_debug_tail_tiles(lm_ctx* ctx, int32_t f, int32_t view, uint8_t* out, int32_t rows, int32_t cols) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
   if (!ctx->tailskip_on) return fail(LM_ERR_INVALID_ARGUMENT, "tail-tile skipping is off");
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  if (f < 0 || f >= L.batch_n || view < 0 || view > 1) return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
-  if (rows != ctx->K.tt_ty[view] || cols != ctx->K.tt_tx[view]) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
-    COPY_SYNC(out, L.tail_flags.p + (int64_t)(f + 1) * ctx->K.tt_slot + ctx->K.tt_off[view], (size_t)rows * cols,
-              hipMemcpyDeviceToHost, L.stream);
+  const auto bad = [&](const Lane& L) -> const char* {
+    if (f < 0 || f >= L.batch_n || view < 0 || view > 1) return "index out of range";
+    if (rows != ctx->K.tt_ty[view] || cols != ctx->K.tt_tx[view]) return "shape mismatch";
+    return nullptr;
+  };
+  return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
+    fetch(out, L.tail_flags.p + (int64_t)(f + 1) * ctx->K.tt_slot + ctx->K.tt_off[view], (size_t)rows * cols);
   });
 }
 
@@ -2163,13 +2179,9 @@ LM_API lm_status lm_debug_point_work(lm_ctx* ctx, int32_t* out) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
   for (int k = 0; k < 2 * LM_NLIST; ++k) out[k] = -1;
   if (!ctx->pointskip_on) return LM_OK;
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
+  return read_delivered(ctx, no_check, [&](const Lane& L, auto fetch) {
     int32_t h[2 * LM_NLIST * LM_TL_NC];
-    COPY_SYNC(h, L.pt_cnt.p, sizeof(h), hipMemcpyDeviceToHost, L.stream);
+    fetch(h, L.pt_cnt.p, sizeof(h));
     for (int l = 0; l < LM_NLIST; ++l) {
       out[2 * l] = std::accumulate(h + l * LM_TL_NC, h + (l + 1) * LM_TL_NC, 0);
       out[2 * l + 1] = std::accumulate(h + (LM_NLIST + l) * LM_TL_NC, h + (LM_NLIST + l + 1) * LM_TL_NC, 0);
@@ -2180,46 +2192,33 @@ LM_API lm_status lm_debug_point_work(lm_ctx* ctx, int32_t* out) {
 LM_API lm_status lm_debug_point_tiles(lm_ctx* ctx, int32_t f, int32_t det, uint8_t* out, int32_t rows, int32_t cols) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
   if (!ctx->pointskip_on) return fail(LM_ERR_INVALID_ARGUMENT, "point-tile skipping is off");
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  if (f < 0 || f >= L.batch_n || det < 0 || det >= LM_NDET || ctx->K.det[det].kind != 0)
-    return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
-  const int view = ctx->K.det[det].view, list = ctx->K.det[det].list;
-  if (rows != ctx->K.fl_ty[view] || cols != ctx->K.fl_tx[view]) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
-    COPY_SYNC(out, L.pt_flags.p + (list & 1) * ctx->K.pt_plane + (int64_t)(f + 1) * ctx->K.fl_slot + ctx->K.fl_off[view],
-              (size_t)rows * cols, hipMemcpyDeviceToHost, L.stream);
+  const auto bad = [&](const Lane& L) -> const char* {
+    if (f < 0 || f >= L.batch_n || det < 0 || det >= LM_NDET || ctx->K.det[det].kind != 0) return "index out of range";
+    const int view = ctx->K.det[det].view;
+    if (rows != ctx->K.fl_ty[view] || cols != ctx->K.fl_tx[view]) return "shape mismatch";
+    return nullptr;
+  };
+  return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
+    const int view = ctx->K.det[det].view, list = ctx->K.det[det].list;
+    fetch(out, L.pt_flags.p + (list & 1) * ctx->K.pt_plane + (int64_t)(f + 1) * ctx->K.fl_slot + ctx->K.fl_off[view],
+          (size_t)rows * cols);
   });
 }
 
 LM_API lm_status lm_debug_tail_mask(lm_ctx* ctx, int32_t f, uint8_t* out, int32_t rows, int32_t cols) {
   if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
-  const Lane* Lp = delivered_lane(ctx);
-  if (!Lp) return fail(LM_ERR_INVALID_ARGUMENT, kLaneReused);
-  const Lane& L = *Lp;
-  if (f < 0 || f >= L.batch_n) return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
-  if (rows != ctx->K.tail_hb || cols != ctx->K.tail_w) return fail(LM_ERR_INVALID_ARGUMENT, "shape mismatch");
-  return guarded([&] {
-    HIPCHK(hipSetDevice(ctx->device));
+  const auto bad = [&](const Lane& L) -> const char* {
+    if (f < 0 || f >= L.batch_n) return "index out of range";
+    if (rows != ctx->K.tail_hb || cols != ctx->K.tail_w) return "shape mismatch";
+    return nullptr;
+  };
+  return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
     const int nb = (cols + 63) / 64;
     std::vector<unsigned long long> bits((size_t)rows * nb);
-    COPY_SYNC(bits.data(), L.tailmask.p + (int64_t)(f + 1) * rows * nb, bits.size() * 8, hipMemcpyDeviceToHost, L.stream);
+    fetch(bits.data(), L.tailmask.p + (int64_t)(f + 1) * rows * nb, bits.size() * 8);
     for (int r = 0; r < rows; ++r)
       for (int x = 0; x < cols; ++x) out[(size_t)r * cols + x] = ((bits[(size_t)r * nb + (x >> 6)] >> (x & 63)) & 1) ? 255 : 0;
   });
-}
-
-LM_API int32_t lm_debug_kernel_times(lm_ctx* ctx, const char** names, double* ms, int32_t cap) {
-  if (!ctx) return 0;
-  const lm_ctx::BatchRec& L = ctx->delivered;
-  const int32_t n = (int32_t)L.t_names.size();
-  for (int32_t i = 0; i < n && i < cap; ++i) {
-    if (names) names[i] = L.t_names[i];
-    if (ms) ms[i] = L.t_ms[i];
-  }
-  return n;
 }
 
 // ------------------------------------------------------- synthetic source
