@@ -87,6 +87,49 @@ lm_status lm_train_patches(lm_train_ctx* ctx, int32_t first, int32_t n, uint8_t*
 lm_status lm_train_solve(lm_train_ctx* ctx, double c_pos, double c_neg, double eps, int32_t max_iter, double* out_W,
                          double* out_rho, lm_train_stats* stats);
 
+/* ---- several problems on the same samples in one pass (cross-validation of the costs).
+ *
+ * Problem p minimises F with its own costs and with C_i = 0 for the samples of
+ * its held-out group.  Starting point, stopping rule, the CG tolerance and
+ * cap, the line search and the scaling of W and rho are lm_train_solve's, and
+ * within one problem every sum is taken in lm_train_solve's order (a sample of
+ * cost 0 adds +-0).  So a problem with held_out = -1 returns, to the bit, what
+ * lm_train_solve returns with its costs, and any problem returns the same
+ * alone or in any company and order. */
+#define LM_TRAIN_MAX_PROBLEMS 64
+#define LM_TRAIN_MAX_GROUPS 256
+
+typedef struct lm_train_problem {
+  double c_pos, c_neg; /* > 0, finite */
+  int32_t held_out;    /* a group whose samples get cost 0 in F, or -1: none */
+  int32_t reserved;    /* 0 */
+} lm_train_problem;
+
+typedef struct lm_train_heldout { /* of the held-out group, at the returned point, from the solver's own z */
+  int32_t n_pos, n_neg;           /* its samples by label */
+  int32_t miss_pos, miss_neg;     /* positives with z <= 0, negatives with z > 0 */
+} lm_train_heldout;
+
+/* Gives stored sample i the group groups[i] in 0..LM_TRAIN_MAX_GROUPS-1; n must
+ * be the number of stored samples.  A later lm_train_add_patches,
+ * lm_train_gather or lm_train_reset forgets the groups. */
+lm_status lm_train_set_groups(lm_train_ctx* ctx, const int32_t* groups, int32_t n);
+
+/* Solves n_problems (1..LM_TRAIN_MAX_PROBLEMS) problems.  out_W: n_problems x
+ * kh*kw doubles, out_rho: n_problems; stats and heldout (n_problems each) may
+ * be NULL.  A held-out group without samples is allowed (counts 0), and so is
+ * one that leaves a single class.  Refused with LM_ERR_INVALID_ARGUMENT before
+ * any launch: what lm_train_solve refuses, n_problems out of range, a cost
+ * that is not positive and finite, reserved != 0, held_out outside -1..255,
+ * held_out >= 0 while no groups are set, and a held-out group that holds every
+ * stored sample. */
+lm_status lm_train_solve_many(lm_train_ctx* ctx, const lm_train_problem* problems, int32_t n_problems, double eps,
+                              int32_t max_iter, double* out_W, double* out_rho, lm_train_stats* stats,
+                              lm_train_heldout* heldout);
+
+/* Problems that share one pass over the sample matrix at this kh x kw; more run as several blocks. */
+int32_t lm_train_problem_block(lm_train_ctx* ctx);
+
 /* z_i = sum W . p_i - rho of any model on the stored samples (out_z: one double per sample). */
 lm_status lm_train_margins(lm_train_ctx* ctx, const double* W, double rho, double* out_z);
 

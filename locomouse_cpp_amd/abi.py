@@ -179,6 +179,7 @@ LM_BKG_MAX_SAMPLES = 65535  # include/locomouse_bkg.h: frames one lm_bkg_ctx acc
 LM_CALIB_MAX_FRAMES, LM_CALIB_MAX_RADIUS, LM_CALIB_MAX_DEGREE = 1 << 20, 4096, 3
 # include/locomouse_train.h
 LM_TRAIN_MAX_SIDE, LM_TRAIN_MAX_SAMPLES = 64, 1 << 22
+LM_TRAIN_MAX_PROBLEMS, LM_TRAIN_MAX_GROUPS = 64, 256
 # include/locomouse_encode.h
 LM_ENC_GRAY8, LM_ENC_RGB24 = 0, 1
 LM_ENC_BLOCK_WORDS, LM_ENC_MAX_HEADER, LM_ENC_MAX_BLOCKS, LM_ENC_MAX_BATCH, LM_ENC_MAX_RADIUS = 52, 640, 1 << 20, 4096, 64
@@ -230,6 +231,14 @@ class lm_train_stats(C.Structure):
         ("converged", C.c_int32),
         ("n_active", C.c_int32),
     ]
+
+
+class lm_train_problem(C.Structure):
+    _fields_ = [("c_pos", C.c_double), ("c_neg", C.c_double), ("held_out", C.c_int32), ("reserved", C.c_int32)]
+
+
+class lm_train_heldout(C.Structure):
+    _fields_ = [("n_pos", C.c_int32), ("n_neg", C.c_int32), ("miss_pos", C.c_int32), ("miss_neg", C.c_int32)]
 
 
 class lm_enc_stats(C.Structure):

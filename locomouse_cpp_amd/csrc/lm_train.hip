@@ -27,6 +27,11 @@
 //   k_train_cg_update  one workgroup: a CG step's scalars and vector updates.
 //   k_train_ls_partials / k_train_ls_pick   the Armijo search over
 //                      lambda = 2^-k from the cached margins, all k at once.
+//   k_train_*_many     the same for the problems of lm_train_solve_many: the
+//                      two matrix passes take a block of problems per
+//                      workgroup and convert a chunk once for all of them, the
+//                      others one problem per workgroup row (further below).
+//   k_train_heldout    the held-out group's samples and misses of a problem.
 //
 // An outer iteration is enqueued whole: the CG steps (a fixed number of
 // them, each a no-op once the residual is small) and the line search read
@@ -40,7 +45,12 @@
 // per-block partials are sized from N before a launch.  The gather writes
 // rows n0 .. n0 + n_points - 1 with n0 + n_points <= max_samples, and its
 // points' frame indices and coordinates are checked on the host; taps outside
-// the corrected image read nothing.
+// the corrected image read nothing.  The _many kernels index a problem's
+// arrays at q * stride with q < the call's problem count, which sizes them
+// (vectors 6 VL, sample arrays 5 N, partials and block sums from N); a block's
+// slots past the last problem read the block's first problem and write nothing;
+// the LDS of k_train_xv_many holds lmt_problem_block x VL doubles, at most 48 KiB
+// (one vector, 32 KB, at 64 x 64); the group bytes are sized by max_samples.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -352,6 +362,418 @@ __global__ __launch_bounds__(kT) void k_train_ls_pick(double* __restrict__ w, co
   if (threadIdx.x == 0 && picked < 0) ctl->ls_fail = 1;
 }
 
+// ---- lm_train_solve_many: the kernels above for several problems on the same
+// samples.  A problem is its costs, its held-out group and its own LmtCtl; its
+// arrays lie `stride` doubles after its predecessor's.  The two matrix passes
+// take a block of pb problems (lmt_problem_block) per workgroup, block b of the
+// call along a grid dimension, and load and convert a 16-byte chunk once for
+// those of them that are live; the other kernels take one problem per
+// workgroup row.  Per problem every sum is the single kernel's, term for term.
+// A problem that is done (converged, or without a line-search step) is gated
+// everywhere, the evaluation included, so its arrays stay as lm_train_solve
+// would have left them at its break; a workgroup whose problems are all gated
+// returns at once, and one with fewer live problems than pb computes for 1, 2
+// or 4 of them.
+
+struct LmtProb {  // a problem in device memory
+  double c_pos, c_neg;
+  int32_t held_out, pad;
+};
+
+struct LmtMany {
+  int n;  // problems of the call
+  const LmtProb* prob;
+  LmtCtl* ctl;
+  const uint8_t* group;  // per sample
+  double* vec;           // per problem w, g, d, r, p, hp: 6 x VL
+  double* smp;           // per problem z, u, a, t, au: 5 x N
+  double* part;          // per problem part_loss, part_act (nb each), lspart (nb x LMT_LS_STEPS)
+  double* xtp;           // per problem nblk x VL
+  int64_t vec_stride, smp_stride, part_stride, xtp_stride;
+};
+enum { V_W = 0, V_G, V_D, V_R, V_P, V_HP };
+enum { S_Z = 0, S_U, S_A, S_T, S_AU, S_NONE = -1 };
+
+DEV bool gated_many(const LmtCtl* ctl, int gate) {
+  return (gate == GATE_CG && (ctl->cg_done || ctl->ls_fail)) || (gate == GATE_CONVERGED && (ctl->converged || ctl->ls_fail));
+}
+
+// The live problems of q0 .. q0 + pb - 1 (those that exist and are not gated),
+// in their order: q[j] is the j-th, q[j] = q[0] from their number on, which is
+// returned.  (Unrolled selects: the list stays in scalar registers.)
+struct LmtLive {
+  int q[LMT_MANY_PB];
+};
+DEV int live_problems(const LmtMany& M, int q0, int pb, int gate, LmtLive& live) {
+  int nl = 0;
+#pragma unroll
+  for (int j = 0; j < LMT_MANY_PB; ++j) live.q[j] = q0;
+#pragma unroll
+  for (int p = 0; p < LMT_MANY_PB; ++p) {
+    if (p < pb && q0 + p < M.n && !gated_many(M.ctl + q0 + p, gate)) {
+#pragma unroll
+      for (int j = 0; j < LMT_MANY_PB; ++j) live.q[j] = j == nl ? q0 + p : live.q[j];
+      nl += 1;
+    }
+  }
+#pragma unroll
+  for (int j = 1; j < LMT_MANY_PB; ++j) live.q[j] = j < nl ? live.q[j] : live.q[0];
+  return nl;
+}
+
+// k_train_xv for NP slots: slot p is live problem p (a slot past the nl live
+// ones computes on the first one's vector and writes nothing).  Entry 16 g + k
+// of slot p's vector is at sv[(k * ncg + g) * NP + p] (lanes of consecutive
+// chunks g read consecutive words), its bias at sv[Dp * NP + p].
+template <int NP>
+DEV void xv_many(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, const LmtMany& M, const LmtLive& live, int nl,
+                 int vi, double div, int ai, int oi, int oai, double* sv) {
+  const int ncg = Dp >> 4, VL = Dp + 1;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const double* v = M.vec + (int64_t)live.q[p] * M.vec_stride + (int64_t)vi * VL;
+    for (int j = threadIdx.x; j < Dp; j += kT) sv[((j & 15) * ncg + (j >> 4)) * NP + p] = v[j];
+    if (threadIdx.x == 0) sv[Dp * NP + p] = v[Dp];
+  }
+  __syncthreads();
+  const int gl = threadIdx.x & (L - 1);
+  const int64_t i0 = ((int64_t)blockIdx.x * (kT / L) + threadIdx.x / L) * kXvS;
+  double acc[NP][kXvS];
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int s = 0; s < kXvS; ++s) acc[p][s] = 0.0;
+  for (int g = gl; g < ncg; g += L) {
+    uint4 q[kXvS];
+#pragma unroll
+    for (int s = 0; s < kXvS; ++s)
+      q[s] = i0 + s < N ? reinterpret_cast<const uint4*>(X + (i0 + s) * Dp)[g] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const double* w = sv + (k * ncg + g) * NP;
+      double wk[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) wk[p] = w[p];
+#pragma unroll
+      for (int s = 0; s < kXvS; ++s) {
+        const uint32_t word = (k >> 2) == 0 ? q[s].x : (k >> 2) == 1 ? q[s].y : (k >> 2) == 2 ? q[s].z : q[s].w;
+        const double x = (double)((word >> (8 * (k & 3))) & 255u);  // once for the NP problems
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[p][s] += x * wk[p];
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    double* smp = M.smp + (int64_t)live.q[p] * M.smp_stride;
+    const double bias = sv[Dp * NP + p];
+#pragma unroll
+    for (int s = 0; s < kXvS; ++s) {
+      double r = acc[p][s];
+      for (int o = L >> 1; o > 0; o >>= 1) r += __shfl_xor(r, o);
+      if (gl == 0 && i0 + s < N && p < nl) {
+        const double z = r / div + bias;
+        smp[(int64_t)oi * N + i0 + s] = z;
+        if (ai != S_NONE) smp[(int64_t)oai * N + i0 + s] = smp[(int64_t)ai * N + i0 + s] * z;
+      }
+    }
+  }
+}
+
+// Sample array oi = X~ (vector vi) of the problems q0 .. q0 + pb - 1, q0 = pb
+// blockIdx.y; with ai, sample array oai = sample array ai times it.
+__global__ __launch_bounds__(kT) void k_train_xv_many(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, LmtMany M,
+                                                      int pb, int vi, double div, int ai, int oi, int oai, int gate) {
+  LmtLive live;
+  const int nl = live_problems(M, blockIdx.y * pb, pb, gate, live);
+  if (nl == 0) return;
+  extern __shared__ double sv[];  // pb x VL doubles
+  if (nl == 1)
+    xv_many<1>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+  else if (nl == 2)
+    xv_many<2>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+  else
+    xv_many<4>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+}
+
+// k_train_xt for NP slots (as xv_many's): the block's sums of X^T t of each,
+// t = the problem's sample array ti.  A chunk is loaded and converted once;
+// the 16 sample lanes are added through LDS one problem after the other.
+template <int NP>
+DEV void xt_many(const uint8_t* __restrict__ X, int64_t N, int Dp, const LmtMany& M, const LmtLive& live, int nl, int ti,
+                 double (*red)[kXtCols], double* redb) {
+  const int cgx = threadIdx.x & 15, sy = threadIdx.x >> 4;
+  const int g = blockIdx.x * 16 + cgx;  // column group of 16
+  const bool cols = g < (Dp >> 4);
+  const bool bias = blockIdx.x == 0 && cgx == 0;
+  const int64_t i0 = (int64_t)blockIdx.y * LMT_XT_BLOCK;
+  const int64_t i1 = i0 + LMT_XT_BLOCK < N ? i0 + LMT_XT_BLOCK : N;
+  const double* t[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) t[p] = M.smp + (int64_t)live.q[p] * M.smp_stride + (int64_t)ti * N;
+  double acc[NP][16], tb[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    tb[p] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[p][k] = 0.0;
+  }
+  if (cols || bias) {
+    for (int64_t i = i0 + sy; i < i1; i += 16) {
+      double tv[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) tv[p] = t[p][i];
+      if (bias) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) tb[p] += tv[p];
+      }
+      if (cols) {
+        const uint4 q = *reinterpret_cast<const uint4*>(X + i * Dp + 16 * g);
+        const uint32_t word[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          const double x = (double)((word[k >> 2] >> (8 * (k & 3))) & 255u);  // once for the NP problems
+#pragma unroll
+          for (int p = 0; p < NP; ++p) acc[p][k] += tv[p] * x;
+        }
+      }
+    }
+  }
+  const int VL = Dp + 1;
+  const int c = blockIdx.x * kXtCols + threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    if (p >= nl) break;          // (uniform)
+    if (p > 0) __syncthreads();  // red is read no more
+#pragma unroll
+    for (int k = 0; k < 16; ++k) red[sy][cgx * 16 + k] = acc[p][k];
+    if (bias) redb[sy] = tb[p];
+    __syncthreads();
+    double* prow = M.xtp + (int64_t)live.q[p] * M.xtp_stride + (int64_t)blockIdx.y * VL;
+    if (c < Dp) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) s += red[q][threadIdx.x];
+      prow[c] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      double s = 0.0;
+      for (int q = 0; q < 16; ++q) s += redb[q];
+      prow[Dp] = s;
+    }
+  }
+}
+
+// The blocks' sums of X^T (sample array ti) of the problems q0 .. q0 + pb - 1, q0 = pb blockIdx.z.
+__global__ __launch_bounds__(kT) void k_train_xt_many(const uint8_t* __restrict__ X, int64_t N, int Dp, LmtMany M, int pb,
+                                                      int ti, int gate) {
+  LmtLive live;
+  const int nl = live_problems(M, blockIdx.z * pb, pb, gate, live);
+  if (nl == 0) return;
+  __shared__ double red[16][kXtCols];
+  __shared__ double redb[16];
+  if (nl == 1)
+    xt_many<1>(X, N, Dp, M, live, nl, ti, red, redb);
+  else if (nl == 2)
+    xt_many<2>(X, N, Dp, M, live, nl, ti, red, redb);
+  else
+    xt_many<4>(X, N, Dp, M, live, nl, ti, red, redb);
+}
+
+// From here on blockIdx.y is the problem.
+
+// vector oi = vector bi + 2 X~^T t from the blocks' sums, in index order
+__global__ __launch_bounds__(kT) void k_train_xt_reduce_many(LmtMany M, int nblk, int Dp, int bi, int oi, int gate) {
+  const int q = blockIdx.y;
+  if (gated_many(M.ctl + q, gate)) return;
+  const int VL = Dp + 1;
+  const int j = blockIdx.x * kT + threadIdx.x;
+  if (j >= VL) return;
+  const double* partial = M.xtp + (int64_t)q * M.xtp_stride;
+  double* vec = M.vec + (int64_t)q * M.vec_stride;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += partial[(int64_t)b * VL + j];
+  if (j < Dp) s = s / 255.0;
+  vec[(int64_t)oi * VL + j] = vec[(int64_t)bi * VL + j] + 2.0 * s;
+}
+
+__global__ __launch_bounds__(kT) void k_train_coef_many(LmtMany M, const int8_t* __restrict__ y, int64_t N, int nb) {
+  const int q = blockIdx.y;
+  if (gated_many(M.ctl + q, GATE_CONVERGED)) return;
+  __shared__ double sh[kT];
+  const LmtProb pr = M.prob[q];
+  double* smp = M.smp + (int64_t)q * M.smp_stride;
+  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+  double loss = 0.0, act = 0.0;
+  if (i < N) {
+    double ti;
+    const double c = lmt_problem_cost(y[i], M.group[i], pr.c_pos, pr.c_neg, pr.held_out);
+    const double ai = lmt_coef(y[i], smp[(int64_t)S_Z * N + i], c, c, &ti, &loss);
+    smp[(int64_t)S_A * N + i] = ai;
+    smp[(int64_t)S_T * N + i] = ti;
+    act = ai != 0.0 ? 1.0 : 0.0;
+  }
+  const double sl = block_sum(loss, sh);
+  const double sa = block_sum(act, sh);
+  if (threadIdx.x == 0) {
+    double* part = M.part + (int64_t)q * M.part_stride;
+    part[blockIdx.x] = sl;
+    part[nb + blockIdx.x] = sa;
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_train_eval_many(LmtMany M, int VL, int nb, double eps, int first) {
+  const int q = blockIdx.x;
+  LmtCtl* ctl = M.ctl + q;
+  if (gated_many(ctl, GATE_CONVERGED)) return;
+  __shared__ double sh[kT];
+  double* vec = M.vec + (int64_t)q * M.vec_stride;
+  const double *w = vec + (int64_t)V_W * VL, *g = vec + (int64_t)V_G * VL;
+  double *d = vec + (int64_t)V_D * VL, *r = vec + (int64_t)V_R * VL, *p = vec + (int64_t)V_P * VL;
+  const double* part = M.part + (int64_t)q * M.part_stride;
+  double ww = 0.0, gg = 0.0;
+  for (int j = threadIdx.x; j < VL; j += kT) {
+    ww += w[j] * w[j];
+    gg += g[j] * g[j];
+    d[j] = 0.0;
+    r[j] = -g[j];
+    p[j] = -g[j];
+  }
+  ww = block_sum(ww, sh);
+  gg = block_sum(gg, sh);
+  const double loss = block_sum_array(part, nb, sh);
+  const double act = block_sum_array(part + nb, nb, sh);
+  if (threadIdx.x == 0) {
+    const double gnorm = sqrt(gg);
+    const double g0 = first ? gnorm : ctl->gnorm0;
+    ctl->f = 0.5 * ww + loss;
+    ctl->gnorm = gnorm;
+    ctl->gnorm0 = g0;
+    ctl->rr = gg;
+    ctl->n_active = (int32_t)act;
+    ctl->converged = gnorm <= eps * g0 ? 1 : 0;
+    ctl->cg_done = ctl->converged;
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_train_cg_update_many(LmtMany M, int VL) {
+  const int q = blockIdx.x;
+  LmtCtl* ctl = M.ctl + q;
+  if (gated_many(ctl, GATE_CG)) return;
+  __shared__ double sh[kT];
+  double* vec = M.vec + (int64_t)q * M.vec_stride;
+  double *d = vec + (int64_t)V_D * VL, *r = vec + (int64_t)V_R * VL, *p = vec + (int64_t)V_P * VL;
+  const double* hp = vec + (int64_t)V_HP * VL;
+  const double rr = ctl->rr, gnorm = ctl->gnorm;
+  double a = 0.0;
+  for (int j = threadIdx.x; j < VL; j += kT) a += p[j] * hp[j];
+  const double php = block_sum(a, sh);
+  const double alpha = rr / php;
+  double b = 0.0;
+  for (int j = threadIdx.x; j < VL; j += kT) {
+    d[j] += alpha * p[j];
+    const double rj = r[j] - alpha * hp[j];
+    r[j] = rj;
+    b += rj * rj;
+  }
+  const double rr1 = block_sum(b, sh);
+  const double beta = rr1 / rr;
+  for (int j = threadIdx.x; j < VL; j += kT) p[j] = r[j] + beta * p[j];
+  if (threadIdx.x == 0) {
+    ctl->rr = rr1;
+    ctl->cg_iters += 1;
+    if (!(sqrt(rr1) > LMT_CG_TOL * gnorm)) ctl->cg_done = 1;
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_train_ls_partials_many(LmtMany M, const int8_t* __restrict__ y, int64_t N,
+                                                               int nb) {
+  const int q = blockIdx.y;
+  if (gated_many(M.ctl + q, GATE_CONVERGED)) return;
+  __shared__ double sh[kT];
+  const LmtProb pr = M.prob[q];
+  const double* smp = M.smp + (int64_t)q * M.smp_stride;
+  double* lspart = M.part + (int64_t)q * M.part_stride + 2 * (int64_t)nb;
+  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+  const bool valid = i < N;
+  const int yi = valid ? y[i] : 1;
+  const double c = valid ? lmt_problem_cost(yi, M.group[i], pr.c_pos, pr.c_neg, pr.held_out) : 0.0;
+  const double zi = valid ? smp[(int64_t)S_Z * N + i] : 0.0, xi = valid ? smp[(int64_t)S_U * N + i] : 0.0;
+  double lambda = 1.0;
+  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
+    const double v = valid ? lmt_ls_delta(yi, zi, xi, lambda, c, c) : 0.0;
+    const double s = block_sum(v, sh);
+    if (threadIdx.x == 0) lspart[(int64_t)blockIdx.x * LMT_LS_STEPS + k] = s;
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_train_ls_pick_many(LmtMany M, int VL, int nb) {
+  const int q = blockIdx.x;
+  LmtCtl* ctl = M.ctl + q;
+  if (gated_many(ctl, GATE_CONVERGED)) return;
+  __shared__ double sh[kT];
+  double* vec = M.vec + (int64_t)q * M.vec_stride;
+  double* w = vec + (int64_t)V_W * VL;
+  const double *g = vec + (int64_t)V_G * VL, *d = vec + (int64_t)V_D * VL;
+  const double* lspart = M.part + (int64_t)q * M.part_stride + 2 * (int64_t)nb;
+  double wd = 0.0, dd = 0.0, gd = 0.0;
+  for (int j = threadIdx.x; j < VL; j += kT) {
+    wd += w[j] * d[j];
+    dd += d[j] * d[j];
+    gd += g[j] * d[j];
+  }
+  wd = block_sum(wd, sh);
+  dd = block_sum(dd, sh);
+  gd = block_sum(gd, sh);
+  int picked = -1;
+  double lambda = 1.0, step = 0.0;
+  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kT) a += lspart[(int64_t)b * LMT_LS_STEPS + k];
+    const double s = block_sum(a, sh);
+    const double delta = lambda * wd + 0.5 * lambda * lambda * dd + s;
+    if (picked < 0 && delta <= LMT_ARMIJO * lambda * gd) {
+      picked = k;
+      step = lambda;
+    }
+  }
+  if (picked >= 0)
+    for (int j = threadIdx.x; j < VL; j += kT) w[j] += step * d[j];
+  if (threadIdx.x == 0 && picked < 0) ctl->ls_fail = 1;
+}
+
+// Per block of kT samples and problem, the held-out group's samples by label
+// and those on the wrong side of z, the margins of the last evaluation:
+// counts[(q * nb + block) * 4 + (n_pos, n_neg, miss_pos, miss_neg)].
+__global__ __launch_bounds__(kT) void k_train_heldout(LmtMany M, const int8_t* __restrict__ y, int64_t N, int nb,
+                                                      int32_t* __restrict__ counts) {
+  const int q = blockIdx.y;
+  __shared__ int32_t sh[4][kT];
+  const int held_out = M.prob[q].held_out;
+  const double* z = M.smp + (int64_t)q * M.smp_stride + (int64_t)S_Z * N;
+  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+  int32_t v[4] = {0, 0, 0, 0};
+  if (i < N && (int)M.group[i] == held_out) {
+    const bool pos = y[i] > 0, above = z[i] > 0.0;
+    v[0] = pos;
+    v[1] = !pos;
+    v[2] = pos && !above;
+    v[3] = !pos && above;
+  }
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) sh[k][t] = v[k];
+  __syncthreads();
+  for (int s = kT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sh[k][t] += sh[k][t + s];
+    }
+    __syncthreads();
+  }
+  if (t < 4) counts[((int64_t)q * nb + blockIdx.x) * 4 + t] = sh[t][0];
+}
+
 }  // namespace
 
 struct lm_train_ctx {
@@ -372,6 +794,15 @@ struct lm_train_ctx {
   DevBuf<LmtCtl> ctl;
   HostBuf<LmtCtl> h_ctl;
   HostBuf<double> h_vec;  // VL
+  // groups (lm_train_set_groups) and the arrays of lm_train_solve_many, sized per call
+  bool groups_set = false;
+  std::vector<uint8_t> h_group;
+  DevBuf<uint8_t> group;  // max_samples; all 0 while no groups are set (no problem holds a group out then)
+  DevBuf<double> m_vec, m_smp, m_part, m_xtp;
+  DevBuf<LmtProb> m_prob;
+  DevBuf<LmtCtl> m_ctl;
+  DevBuf<int32_t> m_counts;
+  HostBuf<LmtCtl> h_m_ctl;  // LM_TRAIN_MAX_PROBLEMS
   // gather
   DevBuf<uint8_t> stage, luts;
   DevBuf<unsigned> mm;
@@ -442,6 +873,7 @@ void commit_labels(lm_train_ctx* c, const int8_t* labels, int64_t n) {
   for (int64_t i = 0; i < n; ++i) c->n_pos += labels[i] > 0;
   c->h_y.insert(c->h_y.end(), labels, labels + n);
   c->n += n;
+  c->groups_set = false;
 }
 
 lm_status gather(lm_train_ctx* c, lm_ctx* det, const uint8_t* frames, int64_t pitch, int32_t n_frames,
@@ -574,6 +1006,7 @@ LM_API lm_status lm_train_reset(lm_train_ctx* ctx) {
   ctx->n = 0;
   ctx->n_pos = 0;
   ctx->h_y.clear();
+  ctx->groups_set = false;
   return LM_OK;
 }
 
@@ -656,6 +1089,194 @@ LM_API lm_status lm_train_solve(lm_train_ctx* ctx, double c_pos, double c_neg, d
       stats->cg_iters = R.cg_iters;
       stats->converged = R.converged;
       stats->n_active = R.n_active;
+    }
+  });
+}
+
+namespace {
+
+void launch_xv_many(lm_train_ctx* c, const LmtMany& M, int vi, int ai, int oi, int oai, int gate) {
+  const int L = lanes_per_sample(c->Dp);
+  const int spb = kT / L * kXvS;
+  const int pb = lmt_problem_block(c->D);
+  const dim3 grid((unsigned)((c->n + spb - 1) / spb), (unsigned)((M.n + pb - 1) / pb));
+  const size_t lds = sizeof(double) * (size_t)pb * (size_t)c->VL;
+  hipLaunchKernelGGL(k_train_xv_many, grid, dim3(kT), lds, c->stream, c->X.p, c->n, c->Dp, L, M, pb, vi, 255.0, ai, oi, oai,
+                     gate);
+}
+
+// vector oi = vector bi + 2 X~^T (sample array ti), per problem
+void launch_xt_many(lm_train_ctx* c, const LmtMany& M, int ti, int bi, int oi, int gate) {
+  const int nblk = (int)((c->n + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
+  const int nchunk = ((c->Dp >> 4) + 15) / 16;
+  const int pb = lmt_problem_block(c->D);
+  const dim3 grid(nchunk, nblk, (M.n + pb - 1) / pb);
+  hipLaunchKernelGGL(k_train_xt_many, grid, dim3(kT), 0, c->stream, c->X.p, c->n, c->Dp, M, pb, ti, gate);
+  hipLaunchKernelGGL(k_train_xt_reduce_many, dim3((c->VL + kT - 1) / kT, M.n), dim3(kT), 0, c->stream, M, nblk, c->Dp,
+                     bi, oi, gate);
+}
+
+// The group bytes in device memory: zeros until groups are set.
+void size_groups(lm_train_ctx* c) {
+  if (c->group.p) return;
+  c->group.alloc((size_t)c->max_samples);
+  SET_SYNC(c->group.p, 0, (size_t)c->max_samples, c->stream);
+}
+
+// Why the problems cannot be solved, or "" (no device call).
+std::string refuse_problems(const lm_train_ctx* c, const lm_train_problem* pr, int32_t n_problems) {
+  if (n_problems < 1 || n_problems > LM_TRAIN_MAX_PROBLEMS)
+    return "n_problems must be in 1.." + std::to_string(LM_TRAIN_MAX_PROBLEMS);
+  std::vector<int64_t> in_group;
+  for (int32_t q = 0; q < n_problems; ++q) {
+    const std::string at = "problem " + std::to_string(q) + ": ";
+    if (!(pr[q].c_pos > 0.0) || !std::isfinite(pr[q].c_pos) || !(pr[q].c_neg > 0.0) || !std::isfinite(pr[q].c_neg))
+      return at + "c_pos and c_neg must be positive and finite";
+    if (pr[q].reserved != 0) return at + "reserved must be 0";
+    if (pr[q].held_out < -1 || pr[q].held_out >= LM_TRAIN_MAX_GROUPS)
+      return at + "held_out must be in -1.." + std::to_string(LM_TRAIN_MAX_GROUPS - 1);
+    if (pr[q].held_out < 0) continue;
+    if (!c->groups_set) return at + "held_out without groups (lm_train_set_groups)";
+    if (in_group.empty()) {
+      in_group.assign(LM_TRAIN_MAX_GROUPS, 0);
+      for (int64_t i = 0; i < c->n; ++i) in_group[c->h_group[(size_t)i]] += 1;
+    }
+    if (in_group[(size_t)pr[q].held_out] == c->n) return at + "its held-out group holds every stored sample";
+  }
+  return "";
+}
+
+}  // namespace
+
+LM_API lm_status lm_train_set_groups(lm_train_ctx* ctx, const int32_t* groups, int32_t n) {
+  if (!ctx || !groups) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
+  if (n != ctx->n)
+    return fail(LM_ERR_INVALID_ARGUMENT,
+                "n is " + std::to_string(n) + ", the context holds " + std::to_string(ctx->n) + " samples");
+  for (int32_t i = 0; i < n; ++i)
+    if (groups[i] < 0 || groups[i] >= LM_TRAIN_MAX_GROUPS)
+      return fail(LM_ERR_INVALID_ARGUMENT, "group " + std::to_string(i) + " is " + std::to_string(groups[i]) +
+                                               ": must be in 0.." + std::to_string(LM_TRAIN_MAX_GROUPS - 1));
+  return guarded([&] {
+    std::vector<uint8_t> g((size_t)n);
+    for (int32_t i = 0; i < n; ++i) g[(size_t)i] = (uint8_t)groups[i];
+    HIPCHK(hipSetDevice(ctx->device));
+    size_groups(ctx);
+    COPY_SYNC(ctx->group.p, g.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+    ctx->h_group.swap(g);
+    ctx->groups_set = true;
+  });
+}
+
+LM_API int32_t lm_train_problem_block(lm_train_ctx* ctx) { return ctx ? lmt_problem_block(ctx->D) : 0; }
+
+LM_API lm_status lm_train_solve_many(lm_train_ctx* ctx, const lm_train_problem* problems, int32_t n_problems,
+                                     double eps, int32_t max_iter, double* out_W, double* out_rho,
+                                     lm_train_stats* stats, lm_train_heldout* heldout) {
+  if (!ctx || !problems || !out_W || !out_rho) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(eps > 0.0) || !std::isfinite(eps)) return fail(LM_ERR_INVALID_ARGUMENT, "eps must be positive and finite");
+  if (max_iter < 0) return fail(LM_ERR_INVALID_ARGUMENT, "max_iter is negative");
+  if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
+  const std::string why = refuse_problems(ctx, problems, n_problems);
+  if (!why.empty()) return fail(LM_ERR_INVALID_ARGUMENT, why);
+  return guarded([&] {
+    lm_train_ctx* c = ctx;
+    HIPCHK(hipSetDevice(c->device));
+    size_groups(c);
+    const int VL = c->VL, P = n_problems;
+    const int64_t N = c->n;
+    const int nb = (int)((N + kT - 1) / kT);
+    const int nblk = (int)((N + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
+    LmtMany M;
+    M.n = P;
+    M.vec_stride = 6 * (int64_t)VL;
+    M.smp_stride = 5 * N;
+    M.part_stride = (int64_t)nb * (2 + LMT_LS_STEPS);
+    M.xtp_stride = (int64_t)nblk * VL;
+    auto size = [](DevBuf<double>& b, size_t n) {
+      if (b.n < n) b.alloc(n);
+    };
+    size(c->m_vec, (size_t)P * (size_t)M.vec_stride);
+    size(c->m_smp, (size_t)P * (size_t)M.smp_stride);
+    size(c->m_part, (size_t)P * (size_t)M.part_stride);
+    size(c->m_xtp, (size_t)P * (size_t)M.xtp_stride);
+    if (c->m_counts.n < (size_t)P * (size_t)nb * 4) c->m_counts.alloc((size_t)P * (size_t)nb * 4);
+    if (!c->m_prob.p) {
+      c->m_prob.alloc(LM_TRAIN_MAX_PROBLEMS);
+      c->m_ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
+      c->h_m_ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
+    }
+    M.prob = c->m_prob.p;
+    M.ctl = c->m_ctl.p;
+    M.group = c->group.p;
+    M.vec = c->m_vec.p;
+    M.smp = c->m_smp.p;
+    M.part = c->m_part.p;
+    M.xtp = c->m_xtp.p;
+    std::vector<LmtProb> pr((size_t)P);
+    for (int q = 0; q < P; ++q) pr[(size_t)q] = LmtProb{problems[q].c_pos, problems[q].c_neg, problems[q].held_out, 0};
+    COPY_SYNC(c->m_prob.p, pr.data(), sizeof(LmtProb) * (size_t)P, hipMemcpyHostToDevice, c->stream);
+    const int cg_cap = c->D + 1 < 96 ? c->D + 1 : 96;
+    HIPCHK(hipMemsetAsync(M.vec, 0, sizeof(double) * (size_t)P * (size_t)M.vec_stride, c->stream));
+    HIPCHK(hipMemsetAsync(M.ctl, 0, sizeof(LmtCtl) * (size_t)P, c->stream));
+    std::vector<int> outer((size_t)P, -1);  // a problem's outer iterations, once it is done
+    const LmtCtl* R = c->h_m_ctl.p;
+    for (int it = 0;; ++it) {
+      launch_xv_many(c, M, V_W, S_NONE, S_Z, S_NONE, GATE_CONVERGED);
+      hipLaunchKernelGGL(k_train_coef_many, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
+      launch_xt_many(c, M, S_T, V_W, V_G, GATE_CONVERGED);
+      hipLaunchKernelGGL(k_train_eval_many, dim3(P), dim3(kT), 0, c->stream, M, VL, nb, eps, it == 0 ? 1 : 0);
+      if (it < max_iter) {
+        for (int k = 0; k < cg_cap; ++k) {
+          launch_xv_many(c, M, V_P, S_A, S_U, S_AU, GATE_CG);
+          launch_xt_many(c, M, S_AU, V_P, V_HP, GATE_CG);
+          hipLaunchKernelGGL(k_train_cg_update_many, dim3(P), dim3(kT), 0, c->stream, M, VL);
+        }
+        launch_xv_many(c, M, V_D, S_NONE, S_U, S_NONE, GATE_CONVERGED);
+        hipLaunchKernelGGL(k_train_ls_partials_many, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
+        hipLaunchKernelGGL(k_train_ls_pick_many, dim3(P), dim3(kT), 0, c->stream, M, VL, nb);
+      }
+      HIPCHK(hipGetLastError());
+      COPY_SYNC(c->h_m_ctl.p, M.ctl, sizeof(LmtCtl) * (size_t)P, hipMemcpyDeviceToHost, c->stream);
+      bool all = true;
+      for (int q = 0; q < P; ++q) {
+        if (outer[(size_t)q] < 0 && (R[q].converged || R[q].ls_fail || it >= max_iter)) outer[(size_t)q] = it;
+        all = all && outer[(size_t)q] >= 0;
+      }
+      if (all) break;
+    }
+    std::vector<int32_t> counts;
+    if (heldout) {
+      hipLaunchKernelGGL(k_train_heldout, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb, c->m_counts.p);
+      HIPCHK(hipGetLastError());
+      counts.resize((size_t)P * (size_t)nb * 4);
+      COPY_SYNC(counts.data(), c->m_counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, c->stream);
+    }
+    std::vector<double> w((size_t)P * (size_t)VL);
+    HIPCHK(hipMemcpy2DAsync(w.data(), sizeof(double) * (size_t)VL, M.vec, sizeof(double) * (size_t)M.vec_stride,
+                            sizeof(double) * (size_t)VL, (size_t)P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int q = 0; q < P; ++q) {
+      const double* wq = w.data() + (size_t)q * (size_t)VL;
+      for (int j = 0; j < c->D; ++j) out_W[(size_t)q * (size_t)c->D + (size_t)j] = wq[j] / 255.0;
+      out_rho[q] = -wq[c->Dp];
+      if (R[q].ls_fail && !R[q].converged) g_err = "the line search found no step (problem " + std::to_string(q) + ")";
+      if (stats) {
+        stats[q].objective = R[q].f;
+        stats[q].grad_norm = R[q].gnorm;
+        stats[q].grad_norm0 = R[q].gnorm0;
+        stats[q].outer_iters = outer[(size_t)q];
+        stats[q].cg_iters = R[q].cg_iters;
+        stats[q].converged = R[q].converged;
+        stats[q].n_active = R[q].n_active;
+      }
+      if (heldout) {
+        int32_t s[4] = {0, 0, 0, 0};
+        for (int b = 0; b < nb; ++b)  // in block order
+          for (int k = 0; k < 4; ++k) s[k] += counts[((size_t)q * (size_t)nb + (size_t)b) * 4 + (size_t)k];
+        heldout[q] = lm_train_heldout{s[0], s[1], s[2], s[3]};
+      }
     }
   });
 }

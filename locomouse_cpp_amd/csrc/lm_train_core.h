@@ -43,6 +43,28 @@ LMT_HD double lmt_coef(int y, double z, double c_pos, double c_neg, double* t, d
   return a;
 }
 
+// The cost C_i of a sample with label y in group `group` for a problem of
+// lm_train_solve_many with costs c_pos, c_neg that holds group `held_out` out
+// (-1: none): 0 for a held-out sample, else the cost of its label.  Handed to
+// lmt_coef and lmt_ls_delta as both costs, a held-out sample's terms are +-0.
+LMT_HD double lmt_problem_cost(int y, int group, double c_pos, double c_neg, int held_out) {
+  return group == held_out ? 0.0 : (y > 0 ? c_pos : c_neg);
+}
+
+// Problems that share one pass over the matrix (lm_train.hip's _many kernels)
+// at D = kh * kw: their vectors, lmt_pitch(D) + 1 doubles each, fit into
+// LMT_MANY_LDS bytes of LDS, so that three workgroups share a CU's 160 KiB; at
+// most LMT_MANY_PB, which the 16 column sums per problem of k_train_xt_many
+// allow in registers.
+#define LMT_MANY_PB 4
+#define LMT_MANY_LDS (48 * 1024)
+LMT_HD int lmt_problem_block(int D) {
+  const int bytes = 8 * ((D + 15) / 16 * 16 + 1);
+  int pb = LMT_MANY_PB;
+  while (pb > 1 && pb * bytes > LMT_MANY_LDS) pb >>= 1;
+  return pb;
+}
+
 // The change of sample i's loss when its margin goes from z to z + lambda xd.
 LMT_HD double lmt_ls_delta(int y, double z, double xd, double lambda, double c_pos, double c_neg) {
   const double yd = (double)y, c = y > 0 ? c_pos : c_neg;
@@ -115,6 +137,52 @@ inline int lmt_host_linesearch(const int8_t* y, const double* z, const double* x
   for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
     double s = 0.0;
     for (int64_t i = 0; i < N; ++i) s += lmt_ls_delta(y[i], z[i], xd[i], lambda, c_pos, c_neg);
+    const double d = lambda * wd + 0.5 * lambda * lambda * dd + s;
+    if (d <= LMT_ARMIJO * lambda * gd) {
+      *dF = d;
+      return k;
+    }
+  }
+  *dF = 0.0;
+  return -1;
+}
+
+// ---- the same for a problem of lm_train_solve_many: group[i] is sample i's
+// group, the samples of group held_out have cost 0 (lmt_problem_cost).  Their
+// terms are +-0, which these sequential sums do not notice: the results equal,
+// to the bit, those of the functions above on the samples that are left.
+
+inline int64_t lmt_host_objective_heldout(const uint8_t* X, int64_t pitch, const int8_t* y, const uint8_t* group,
+                                          int64_t N, int D, double c_pos, double c_neg, int held_out, const double* wb,
+                                          double* z, double* a, double* t, double* F, double* grad) {
+  lmt_host_margins(X, pitch, N, D, wb, z);
+  double f = 0.0;
+  int64_t n_active = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    double loss;
+    const double c = lmt_problem_cost(y[i], group[i], c_pos, c_neg, held_out);
+    a[i] = lmt_coef(y[i], z[i], c, c, &t[i], &loss);
+    f += loss;
+    n_active += a[i] != 0.0;
+  }
+  double reg = 0.0;
+  for (int j = 0; j <= D; ++j) reg += wb[j] * wb[j];
+  *F = 0.5 * reg + f;
+  lmt_host_xt(X, pitch, N, D, t, grad);
+  for (int j = 0; j <= D; ++j) grad[j] = wb[j] + 2.0 * grad[j];
+  return n_active;
+}
+
+inline int lmt_host_linesearch_heldout(const int8_t* y, const uint8_t* group, const double* z, const double* xd,
+                                       int64_t N, double c_pos, double c_neg, int held_out, double wd, double dd,
+                                       double gd, double* dF) {
+  double lambda = 1.0;
+  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
+    double s = 0.0;
+    for (int64_t i = 0; i < N; ++i) {
+      const double c = lmt_problem_cost(y[i], group[i], c_pos, c_neg, held_out);
+      s += lmt_ls_delta(y[i], z[i], xd[i], lambda, c, c);
+    }
     const double d = lambda * wd + 0.5 * lambda * lambda * dd + s;
     if (d <= LMT_ARMIJO * lambda * gd) {
       *dF = d;

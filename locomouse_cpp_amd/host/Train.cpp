@@ -95,6 +95,99 @@ void parse_train_spec(const std::string& spec, TrainOptions& opt) {
   if (part.size() > 4) opt.neg_per_frame = whole(part[4], "neg_per_frame", 0, 100000);
 }
 
+void parse_train_cv_spec(const std::string& spec, TrainOptions& opt) {
+  const std::string form = "LM_TRAIN_CV: expected folds:s1,s2,..., not " + spec + ".";
+  const size_t colon = spec.find(':');
+  if (colon == std::string::npos || spec.find(':', colon + 1) != std::string::npos) throw std::invalid_argument(form);
+  const std::string fs = spec.substr(0, colon);
+  long folds = 0;
+  bool ok = !fs.empty() && fs.size() <= 9;
+  for (char ch : fs) {
+    if (ch < '0' || ch > '9') ok = false;
+    if (ok) folds = folds * 10 + (ch - '0');
+  }
+  if (!ok || folds < 2 || folds > 16)
+    throw std::invalid_argument("LM_TRAIN_CV: folds must be a whole number in 2..16, not " + fs + ".");
+  std::vector<std::string> part(1);
+  for (char ch : spec.substr(colon + 1)) {
+    if (ch == ',')
+      part.emplace_back();
+    else
+      part.back().push_back(ch);
+  }
+  std::vector<double> scales;
+  for (const std::string& t : part) {
+    size_t used = 0;
+    double v = 0;
+    try {
+      v = std::stod(t, &used);
+    } catch (const std::exception&) {
+      used = 0;
+    }
+    if (t.empty() || t[0] == ' ' || t[0] == '\t' || used != t.size() || !(v > 0) || !std::isfinite(v))
+      throw std::invalid_argument("LM_TRAIN_CV: a scale must be a positive number, not \"" + t + "\".");
+    if (std::find(scales.begin(), scales.end(), v) != scales.end())
+      throw std::invalid_argument("LM_TRAIN_CV: scale " + t + " is given twice.");
+    scales.push_back(v);
+  }
+  if (scales.size() > 16) throw std::invalid_argument("LM_TRAIN_CV: at most 16 scales, not " + std::to_string(scales.size()) + ".");
+  if (folds * (long)scales.size() > LM_TRAIN_MAX_PROBLEMS)
+    throw std::invalid_argument("LM_TRAIN_CV: folds x scales must be at most " + std::to_string(LM_TRAIN_MAX_PROBLEMS) +
+                                ", not " + std::to_string(folds * (long)scales.size()) + ".");
+  opt.cv_folds = (int)folds;
+  opt.cv_scales = scales;
+}
+
+std::vector<int32_t> cv_fold_of_samples(const std::vector<int>& sample_frames, int folds) {
+  std::vector<int> frames = sample_frames;
+  std::sort(frames.begin(), frames.end());
+  frames.erase(std::unique(frames.begin(), frames.end()), frames.end());
+  std::vector<int32_t> out;
+  for (int f : sample_frames)
+    out.push_back((int32_t)((std::lower_bound(frames.begin(), frames.end(), f) - frames.begin()) % folds));
+  return out;
+}
+
+namespace {
+
+// The sum of a row's error terms as num / den (the score is half of it).
+void cv_fraction(const CvRow& r, __int128& num, __int128& den) {
+  if (r.n_pos > 0 && r.n_neg > 0) {
+    num = (__int128)r.miss_pos * r.n_neg + (__int128)r.miss_neg * r.n_pos;
+    den = (__int128)r.n_pos * r.n_neg;
+  } else if (r.n_pos > 0) {
+    num = r.miss_pos;
+    den = r.n_pos;
+  } else if (r.n_neg > 0) {
+    num = r.miss_neg;
+    den = r.n_neg;
+  } else {
+    num = 0;
+    den = 1;
+  }
+}
+
+}  // namespace
+
+int cv_select(std::vector<CvRow>& rows) {
+  int best = -1;
+  __int128 bn = 0, bd = 1;
+  for (size_t k = 0; k < rows.size(); ++k) {
+    __int128 n, d;
+    cv_fraction(rows[k], n, d);
+    rows[k].score = 0.5 * ((double)n / (double)d);
+    // n / d < bn / bd  <=>  n bd < bn d (counts are below 2^31: the products fit)
+    const bool less = best < 0 || n * bd < bn * d;
+    const bool equal = best >= 0 && n * bd == bn * d;
+    if (less || (equal && rows[k].scale < rows[(size_t)best].scale)) {
+      best = (int)k;
+      bn = n;
+      bd = d;
+    }
+  }
+  return best;
+}
+
 std::vector<TrainPoint> select_mined(const std::vector<TrainPoint>& candidates, const std::vector<TrainPoint>& labels,
                                      int r_neg, TrainSeen& seen) {
   std::multimap<int, const TrainPoint*> by_frame;
@@ -153,6 +246,28 @@ void check_train_labels(const LocoMouse_Inputs& in, const TrainLabels& labels) {
     }
   }
   if (!any) throw std::invalid_argument("no feature to train.");
+}
+
+void check_train_cv(const TrainLabels& labels, const TrainOptions& opt) {
+  if (opt.cv_folds == 0) return;
+  const size_t ns = opt.cv_scales.size();
+  if (opt.cv_folds < 2 || opt.cv_folds > 16 || ns < 1 || ns > 16 || (size_t)opt.cv_folds * ns > LM_TRAIN_MAX_PROBLEMS)
+    throw std::invalid_argument("LM_TRAIN_CV: folds must be in 2..16, with 1..16 scales and folds x scales at most " +
+                                std::to_string(LM_TRAIN_MAX_PROBLEMS) + ".");
+  for (size_t k = 0; k < ns; ++k) {
+    const double v = opt.cv_scales[k];
+    if (!(v > 0) || !std::isfinite(v) || std::count(opt.cv_scales.begin(), opt.cv_scales.end(), v) != 1)
+      throw std::invalid_argument("LM_TRAIN_CV: the scales must be positive and finite, each at most once.");
+  }
+  for (int f = 0; f < TF_COUNT; ++f) {
+    if (!labels.requested[f]) continue;
+    std::set<int> frames;
+    for (const TrainPoint& p : labels.points[f]) frames.insert(p.frame);
+    if ((int)frames.size() < opt.cv_folds)
+      throw std::invalid_argument(std::string("LM_TRAIN_CV: labels_") + kTrainFeatureNames[f] + " has " +
+                                  std::to_string(frames.size()) + " labelled frames, fewer than the " +
+                                  std::to_string(opt.cv_folds) + " folds.");
+  }
 }
 
 namespace {
@@ -232,9 +347,11 @@ struct Session {
   }
 
   // One patch per point through det's read of the frames, in chunks of `batch` frames.
-  void gather(lm_train_ctx* tr, lm_ctx* det, std::vector<TrainPoint> pts, int label) {
+  // `sample_frame` grows by the points' frames in the order their samples are stored.
+  void gather(lm_train_ctx* tr, lm_ctx* det, std::vector<TrainPoint> pts, int label, std::vector<int>& sample_frame) {
     const auto t0 = std::chrono::steady_clock::now();
     std::stable_sort(pts.begin(), pts.end(), [](const TrainPoint& a, const TrainPoint& b) { return a.frame < b.frame; });
+    for (const TrainPoint& p : pts) sample_frame.push_back(p.frame);
     const int batch = std::max(in.batch, 1);
     std::vector<lm_train_point> chunk;
     for (size_t k = 0; k < pts.size();) {
@@ -289,17 +406,48 @@ struct Session {
     return out;
   }
 
-  void solve(lm_train_ctx* tr, Model& model, int feature, TrainReport::Feature& fr) {
+  void solve(lm_train_ctx* tr, Model& model, int feature, TrainReport::Feature& fr, double scale = 1.0) {
     const auto t0 = std::chrono::steady_clock::now();
     const int slot = model_slot(feature);
     lm_detector* d = model.detector(slot);
     std::vector<double> W((size_t)d->rows * d->cols);
     double rho = 0;
-    check(lm_train_solve(tr, opt.c_pos, opt.c_neg, opt.eps, opt.max_iter, W.data(), &rho, &fr.stats), "lm_train_solve");
+    // (scale 1 leaves the spec's own costs to the bit)
+    check(lm_train_solve(tr, opt.c_pos * scale, opt.c_neg * scale, opt.eps, opt.max_iter, W.data(), &rho, &fr.stats),
+          "lm_train_solve");
     model.w[slot] = W;
     model.rebind();
     d->bias = rho;
     rep.solve_s += seconds_since(t0);
+  }
+
+  // Scores every scale of opt.cv_scales by cross-validation over the stored
+  // samples' frames (Train.hpp) and returns the chosen one.
+  double cross_validate(lm_train_ctx* tr, const std::vector<int>& sample_frame, int kh, int kw, TrainReport::Feature& fr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<int32_t> fold = cv_fold_of_samples(sample_frame, opt.cv_folds);
+    check(lm_train_set_groups(tr, fold.data(), (int32_t)fold.size()), "lm_train_set_groups");
+    const size_t ns = opt.cv_scales.size();
+    std::vector<lm_train_problem> problems;
+    for (int f = 0; f < opt.cv_folds; ++f)
+      for (double s : opt.cv_scales) problems.push_back(lm_train_problem{opt.c_pos * s, opt.c_neg * s, f, 0});
+    std::vector<double> W(problems.size() * (size_t)kh * (size_t)kw), rho(problems.size());
+    std::vector<lm_train_heldout> held(problems.size());
+    check(lm_train_solve_many(tr, problems.data(), (int32_t)problems.size(), opt.eps, opt.max_iter, W.data(), rho.data(),
+                              nullptr, held.data()),
+          "lm_train_solve_many");
+    fr.cv.assign(ns, CvRow());
+    for (size_t q = 0; q < problems.size(); ++q) {
+      CvRow& r = fr.cv[q % ns];
+      r.scale = opt.cv_scales[q % ns];
+      r.n_pos += held[q].n_pos;
+      r.n_neg += held[q].n_neg;
+      r.miss_pos += held[q].miss_pos;
+      r.miss_neg += held[q].miss_neg;
+    }
+    fr.cv_scale = fr.cv[(size_t)cv_select(fr.cv)].scale;
+    rep.cv_s += seconds_since(t0);
+    return fr.cv_scale;
   }
 
   void train_feature(int feature, const std::vector<TrainPoint>& labels, Model& model) {
@@ -329,8 +477,9 @@ struct Session {
                           &T.c),
           "lm_train_create");
     std::unique_ptr<LocoMouse> L = mirror(model.m);
-    gather(T.c, L->context(), labels, 1);
-    gather(T.c, L->context(), negatives, -1);
+    std::vector<int> sample_frame;
+    gather(T.c, L->context(), labels, 1, sample_frame);
+    gather(T.c, L->context(), negatives, -1, sample_frame);
     solve(T.c, model, feature, fr);
     for (int round = 0; mine && round < opt.rounds; ++round) {
       const auto t0 = std::chrono::steady_clock::now();
@@ -349,9 +498,10 @@ struct Session {
       if ((int64_t)mined.size() > left) mined.resize((size_t)std::max<int64_t>(left, 0));
       fr.mined.push_back((int)mined.size());
       if (mined.empty()) break;
-      gather(T.c, L->context(), mined, -1);
+      gather(T.c, L->context(), mined, -1, sample_frame);
       solve(T.c, model, feature, fr);
     }
+    if (opt.cv_folds > 0) solve(T.c, model, feature, fr, cross_validate(T.c, sample_frame, kh, kw, fr));
     rep.features.push_back(fr);
   }
 };
@@ -361,6 +511,7 @@ struct Session {
 void train_detectors(const LocoMouse_Inputs& in, const TrainLabels& labels, const TrainOptions& opt, const Model& base,
                      Model& out, TrainReport* report) {
   check_train_labels(in, labels);
+  check_train_cv(labels, opt);
   if (!(opt.c_pos > 0) || !(opt.c_neg > 0) || !(opt.eps > 0) || opt.rounds < 0 || opt.neg_per_frame < 0)
     throw std::invalid_argument("train_detectors: c_pos, c_neg and eps must be positive, rounds and neg_per_frame not negative.");
   Session S(in, opt);

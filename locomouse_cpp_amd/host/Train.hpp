@@ -19,6 +19,17 @@
 //               (deduplicated by (frame, x, y)), and solve again; a round that
 //               adds none ends it.  The tail detectors have no candidate list:
 //               they are solved once.
+//   costs       with cv_folds > 0, after the last mining round: the costs are
+//               scaled by each of cv_scales in turn and scored by k-fold
+//               cross-validation over the feature's labelled frames (frame
+//               rank r of the sorted frames is fold r mod cv_folds, and every
+//               sample of a frame, label, initial or mined negative, takes its
+//               frame's fold), all folds x scales problems in one
+//               lm_train_solve_many call; the scale with the smallest balanced
+//               error of the held-out samples wins, and the detector is
+//               lm_train_solve on all samples with the costs times that scale.
+//               The mining rounds before it ran with the spec's own costs and
+//               are not repeated.
 #ifndef LOCOMOUSE_HOST_TRAIN_HPP
 #define LOCOMOUSE_HOST_TRAIN_HPP
 
@@ -48,15 +59,29 @@ struct TrainOptions {
   int rounds = 2, neg_per_frame = 60;
   int r_neg = 0;       // 0: max(kh, kw) / 4
   int max_iter = 200;  // outer iterations of a solve
+  int cv_folds = 0;    // 0: no cross-validation; else 2..16
+  std::vector<double> cv_scales;  // 1..16 distinct positive scales of (c_pos, c_neg); cv_folds x scales <= LM_TRAIN_MAX_PROBLEMS
 };
 
 // "c_pos:c_neg:eps:rounds:neg_per_frame" (the LM_TRAIN knob; trailing fields
 // may be left out); throws std::invalid_argument("LM_TRAIN: ...").
 void parse_train_spec(const std::string& spec, TrainOptions& opt);
 
+// "folds:s1,s2,..." (the LM_TRAIN_CV knob): folds in 2..16, 1..16 scales, each
+// positive and finite and at most once, folds x scales <= LM_TRAIN_MAX_PROBLEMS;
+// throws std::invalid_argument("LM_TRAIN_CV: ...").
+void parse_train_cv_spec(const std::string& spec, TrainOptions& opt);
+
 struct TrainLabels {
   bool requested[TF_COUNT] = {false, false, false, false, false, false};
   std::vector<TrainPoint> points[TF_COUNT];
+};
+
+// A cost scale's held-out counts pooled over the folds (every sample is held out exactly once).
+struct CvRow {
+  double scale = 0;
+  int64_t n_pos = 0, n_neg = 0, miss_pos = 0, miss_neg = 0;
+  double score = 0;  // the balanced error 1/2 (miss_pos / n_pos + miss_neg / n_neg); a class without samples leaves its term out
 };
 
 struct TrainReport {
@@ -64,10 +89,21 @@ struct TrainReport {
     int feature = -1, n_pos = 0, n_neg_initial = 0;
     std::vector<int> mined;  // negatives added per mining round
     lm_train_stats stats{};  // of the last solve
+    std::vector<CvRow> cv;   // with cv_folds > 0: one row per scale, in cv_scales' order
+    double cv_scale = 0;     // the chosen scale
   };
   std::vector<Feature> features;
-  double gather_s = 0, solve_s = 0, mining_s = 0;
+  double gather_s = 0, solve_s = 0, mining_s = 0, cv_s = 0;
 };
+
+// The fold of every sample: sample_frames[i] is sample i's video frame; the
+// distinct frames are sorted and frame rank r is fold r mod folds.  Pure host code.
+std::vector<int32_t> cv_fold_of_samples(const std::vector<int>& sample_frames, int folds);
+
+// Fills every row's score and returns the index of the row with the smallest;
+// a tie goes to the smaller scale, which regularises more.  Scores are
+// compared exactly, as the fractions of integers they are.  Pure host code.
+int cv_select(std::vector<CvRow>& rows);
 
 // The mined negatives of one round: the candidates, in their order, that are at
 // Chebyshev distance >= r_neg from every label of their frame and whose
@@ -84,6 +120,10 @@ std::vector<TrainPoint> initial_negatives(int feature, int frame, const std::vec
 // outside the corrected image, a requested feature without labels): throws
 // std::invalid_argument.  No device call.
 void check_train_labels(const LocoMouse_Inputs& in, const TrainLabels& labels);
+
+// With opt.cv_folds > 0: every requested feature has at least cv_folds labelled
+// frames, and the folds and scales are in range; throws std::invalid_argument.
+void check_train_cv(const TrainLabels& labels, const TrainOptions& opt);
 
 // Trains every requested feature in turn, each on top of the detectors
 // trained before it; out starts as a copy of base.  Reads the labelled frames

@@ -16,7 +16,10 @@
 // LM_TRAIN=c_pos:c_neg:eps:rounds:neg_per_frame (10:1:1e-6:2:60); LM_METHOD:
 // the LocoMouse method whose frame normalisation is used (0); LM_DEVICE,
 // LM_BATCH, LM_BACKGROUND, LM_READ_THREADS as for LocoMouse; LM_TIMING prints
-// the gather, solve and mining times.  Malformed input is an
+// the gather, solve, mining and cross-validation times.  LM_TRAIN_CV=folds:s1,s2,...
+// (off): the costs are scaled by each s in turn, scored by cross-validation
+// over the labelled frames in `folds` folds, and the best scale trains the
+// detector (Train.hpp); a line per feature prints the table.  Malformed input is an
 // "Invalid inputs: ..." error before a device is touched.  Exit code 1 on any
 // error.
 #include <algorithm>
@@ -102,6 +105,7 @@ int run(int argc, char** argv) {
   load_labels(labels_file, wanted, labels);
   TrainOptions opt;
   if (const char* spec = std::getenv("LM_TRAIN")) parse_train_spec(spec, opt);
+  if (const char* spec = std::getenv("LM_TRAIN_CV")) parse_train_cv_spec(spec, opt);
   int method = 0;
   if (const char* m = std::getenv("LM_METHOD")) {
     method = std::atoi(m);
@@ -122,6 +126,7 @@ int run(int argc, char** argv) {
   li.setup.view_box_bottom = cal.bottom_view;
   li.model = base.m;
   check_train_labels(li, labels);
+  check_train_cv(labels, opt);
   {  // the output must be writable before the work is done
     std::FILE* f = std::fopen(model_out.c_str(), "a");
     if (!f) throw std::invalid_argument("Could not create the model file: " + model_out + ".");
@@ -154,11 +159,18 @@ int run(int argc, char** argv) {
     std::cout << "; objective " << f.stats.objective << ", gradient " << f.stats.grad_norm << " of "
               << f.stats.grad_norm0 << ", " << f.stats.outer_iters << " outer and " << f.stats.cg_iters
               << " CG iterations, " << (f.stats.converged ? "converged" : "NOT converged") << std::endl;
+    if (!f.cv.empty()) {
+      std::cout << kTrainFeatureNames[f.feature] << " cv: " << opt.cv_folds << " folds;";
+      for (const CvRow& r : f.cv)
+        std::cout << " scale " << r.scale << ": missed " << r.miss_pos << "/" << r.n_pos << " positives, " << r.miss_neg
+                  << "/" << r.n_neg << " negatives, score " << r.score << ";";
+      std::cout << " chosen scale " << f.cv_scale << std::endl;
+    }
   }
   std::cout << "Model written to " << model_out << std::endl;
   if (std::getenv("LM_TIMING"))
     std::cout << "LM_TIMING gather_ms " << 1e3 * rep.gather_s << " solve_ms " << 1e3 * rep.solve_s << " mining_ms "
-              << 1e3 * rep.mining_s << std::endl;
+              << 1e3 * rep.mining_s << " cv_ms " << 1e3 * rep.cv_s << std::endl;
   return EXIT_SUCCESS;
 }
 

@@ -12,8 +12,8 @@ import numpy as np
 
 from .abi import (BB_FRAME_DTYPE, CALIB_RECORD_DTYPE, LM_ENC_GRAY8, LM_ENC_RGB24, LM_OK, lm_batch_result, lm_bb_result,
                   lm_calib_fit_result, lm_calib_opts, lm_calib_record, lm_enc_mark, lm_enc_overlay, lm_enc_result,
-                  lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_interval_stats, lm_jpeg_stats, lm_train_point,
-                  lm_train_stats, result_to_numpy)
+                  lm_enc_stats, lm_geometry, lm_jpeg_info, lm_jpeg_interval_stats, lm_jpeg_stats, lm_train_heldout,
+                  lm_train_point, lm_train_problem, lm_train_stats, result_to_numpy)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -63,7 +63,8 @@ ENC_EXPORTED = ("lm_enc_slot_bytes", "lm_enc_slot_bytes_restart", "lm_enc_create
 # include/locomouse_train.h (detector weights trained from labelled patches), same library
 TRAIN_EXPORTED = ("lm_train_create", "lm_train_destroy", "lm_train_add_patches", "lm_train_gather",
                   "lm_train_gather_device", "lm_train_samples", "lm_train_reset", "lm_train_patches", "lm_train_solve",
-                  "lm_train_margins", "lm_train_stream")
+                  "lm_train_margins", "lm_train_stream", "lm_train_set_groups", "lm_train_solve_many",
+                  "lm_train_problem_block")
 TRAIN_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTrain")
 TRANSCODE_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseTranscode")
 
@@ -279,6 +280,11 @@ def lib():
                                      C.POINTER(C.c_double), C.POINTER(lm_train_stats)]
         L.lm_train_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         L.lm_train_stream.argtypes = [C.c_void_p]
+        L.lm_train_set_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.lm_train_solve_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        L.lm_train_problem_block.argtypes = [C.c_void_p]
+        L.lm_train_problem_block.restype = C.c_int32
         L.lm_train_stream.restype = C.c_void_p
         L.lm_calib_default_opts.argtypes = [C.POINTER(lm_calib_opts)]
         L.lm_calib_default_opts.restype = None
@@ -865,6 +871,33 @@ class Trainer:
         st = lm_train_stats()
         _check(lib().lm_train_solve(self._h, c_pos, c_neg, eps, max_iter, W.ctypes.data, C.byref(rho), C.byref(st)))
         return W, rho.value, {n: getattr(st, n) for n, _ in lm_train_stats._fields_}
+
+    def set_groups(self, groups):
+        """A group in 0..255 for every stored sample (the folds of a cross-validation);
+        forgotten by the next add_patches, gather or reset."""
+        g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        _check(lib().lm_train_set_groups(self._h, g.ctypes.data, len(g)))
+
+    def problem_block(self):
+        """Problems that share one pass over the sample matrix at this kh x kw."""
+        return int(lib().lm_train_problem_block(self._h))
+
+    def solve_many(self, problems, eps=1e-6, max_iter=100):
+        """problems: [(c_pos, c_neg, held_out)], held_out a group or -1.  Returns
+        (Ws, rhos, stats, heldout): per problem W [kh, kw] float64, rho, the
+        stats dict and the held-out group's counts {n_pos, n_neg, miss_pos,
+        miss_neg}, each problem's what it gets alone."""
+        n = len(problems)
+        pr = (lm_train_problem * max(n, 1))(*[lm_train_problem(float(a), float(b), int(h), 0) for a, b, h in problems])
+        W = np.zeros((max(n, 1), self.kh, self.kw), np.float64)
+        rho = np.zeros(max(n, 1), np.float64)
+        st = (lm_train_stats * max(n, 1))()
+        ho = (lm_train_heldout * max(n, 1))()
+        _check(lib().lm_train_solve_many(self._h, C.addressof(pr), n, eps, max_iter, W.ctypes.data, rho.ctypes.data,
+                                         C.addressof(st), C.addressof(ho)))
+        return ([W[q].copy() for q in range(n)], [float(rho[q]) for q in range(n)],
+                [{k: getattr(st[q], k) for k, _ in lm_train_stats._fields_} for q in range(n)],
+                [{k: getattr(ho[q], k) for k, _ in lm_train_heldout._fields_} for q in range(n)])
 
     def margins(self, W, rho):
         """z_i = sum(W * patch_i) - rho of the stored samples."""
