@@ -90,12 +90,12 @@ lm_status lm_train_solve(lm_train_ctx* ctx, double c_pos, double c_neg, double e
 /* ---- several problems on the same samples in one pass (cross-validation of the costs).
  *
  * Problem p minimises F with its own costs and with C_i = 0 for the samples of
- * its held-out group.  Starting point, stopping rule, the CG tolerance and
- * cap, the line search and the scaling of W and rho are lm_train_solve's, and
- * within one problem every sum is taken in lm_train_solve's order (a sample of
- * cost 0 adds +-0).  So a problem with held_out = -1 returns, to the bit, what
- * lm_train_solve returns with its costs, and any problem returns the same
- * alone or in any company and order. */
+ * its held-out group.  There is one solver: lm_train_solve is the call of the
+ * one problem {c_pos, c_neg, held_out = -1}, so starting point, stopping rule,
+ * the CG tolerance and cap, the line search and the scaling of W and rho are
+ * the same.  Within one problem every sum is taken in an order that depends on
+ * the samples alone (a sample of cost 0 adds +-0), so any problem returns the
+ * same, to the bit, alone or in any company and order. */
 #define LM_TRAIN_MAX_PROBLEMS 64
 #define LM_TRAIN_MAX_GROUPS 256
 

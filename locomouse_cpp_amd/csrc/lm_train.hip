@@ -9,12 +9,22 @@
 //
 //   k_train_gather     one workgroup per point: its kh x kw taps through
 //                      ipad_pixel (lm_dev_common.h), the read of k_ingest.
+//
+// One solver: lm_train_solve is a call of one problem, lm_train_solve_many of
+// up to LM_TRAIN_MAX_PROBLEMS on the same samples, lm_train_margins one X~ v
+// pass of one problem.  A problem is its costs and its held-out group; its
+// arrays lie one after the other problem's (LmtLayout, lm_train_core.h).  The
+// two matrix passes take a block of problems (lmt_problem_block) per workgroup
+// and convert a chunk of the matrix once for all of them, the other kernels
+// one problem per workgroup row.
+//
 //   k_train_xv         out = X~ v: L = 2^k lanes per sample (L >= D / 16, at
 //                      most 64) and four consecutive samples per lane group,
-//                      so 256 / L samples per wave; v in LDS; a lane loads 16
-//                      bytes of each of its samples' rows at a time; the L
-//                      lanes' sums are folded by xor butterflies (the same
-//                      pairs whatever the lane, so every lane has the sum).
+//                      so 256 / L samples per wave; the problems' v in LDS; a
+//                      lane loads 16 bytes of each of its samples' rows at a
+//                      time; the L lanes' sums are folded by xor butterflies
+//                      (the same pairs whatever the lane, so every lane has
+//                      the sum).
 //   k_train_xt         X^T t: a workgroup takes LMT_XT_BLOCK samples and 256
 //                      columns; a thread owns 16 columns, accumulates them in
 //                      registers over every 16th sample of the block, the 16
@@ -27,29 +37,26 @@
 //   k_train_cg_update  one workgroup: a CG step's scalars and vector updates.
 //   k_train_ls_partials / k_train_ls_pick   the Armijo search over
 //                      lambda = 2^-k from the cached margins, all k at once.
-//   k_train_*_many     the same for the problems of lm_train_solve_many: the
-//                      two matrix passes take a block of problems per
-//                      workgroup and convert a chunk once for all of them, the
-//                      others one problem per workgroup row (further below).
 //   k_train_heldout    the held-out group's samples and misses of a problem.
 //
 // An outer iteration is enqueued whole: the CG steps (a fixed number of
 // them, each a no-op once the residual is small) and the line search read
-// their flags from the control block in device memory, and the host reads
-// that block once per outer iteration.  Every sum is taken in an order that
-// depends on N and D alone: strided per-thread sums, then a binary tree in
-// LDS; blocks of samples in index order.  No atomics.
+// their flags from the problem's control block in device memory, and the host
+// reads the blocks once per outer iteration.  Every sum is taken in an order
+// that depends on N and D alone: strided per-thread sums, then a binary tree
+// in LDS; blocks of samples in index order.  No atomics.
 //
 // Safety: sample rows are read at i * Dp for i < N <= max_samples, which
-// sizes the matrix; vectors have VL entries and are indexed below VL; the
-// per-block partials are sized from N before a launch.  The gather writes
-// rows n0 .. n0 + n_points - 1 with n0 + n_points <= max_samples, and its
-// points' frame indices and coordinates are checked on the host; taps outside
-// the corrected image read nothing.  The _many kernels index a problem's
-// arrays at q * stride with q < the call's problem count, which sizes them
-// (vectors 6 VL, sample arrays 5 N, partials and block sums from N); a block's
+// sizes the matrix; vectors have VL entries and are indexed below VL.  The
+// gather writes rows n0 .. n0 + n_points - 1 with n0 + n_points <= max_samples,
+// and its points' frame indices and coordinates are checked on the host; taps
+// outside the corrected image read nothing.  The solver's kernels index a
+// problem's arrays at q * stride with q < the call's problem count; strides
+// and sizes are LmtLayout's for the N and VL of the call (bind_problems): the
+// vectors V_W .. V_HP, the sample arrays S_Z .. S_AU, two nb-long parts and
+// nb x LMT_LS_STEPS of lspart, nblk rows of block sums, nb x 4 counts; a block's
 // slots past the last problem read the block's first problem and write nothing;
-// the LDS of k_train_xv_many holds lmt_problem_block x VL doubles, at most 48 KiB
+// the LDS of k_train_xv holds lmt_problem_block x VL doubles, at most 48 KiB
 // (one vector, 32 KB, at 64 x 64); the group bytes are sized by max_samples.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,10 +83,6 @@ struct LmtCtl {  // the solver's scalars in device memory
   int32_t converged, cg_done, cg_iters, n_active, ls_fail;
 };
 enum { GATE_NONE = 0, GATE_CG = 1, GATE_CONVERGED = 2 };
-
-DEV bool gated(const LmtCtl* ctl, int gate) {
-  return (gate == GATE_CG && ctl->cg_done) || (gate == GATE_CONVERGED && (ctl->converged || ctl->ls_fail));
-}
 
 // Sum of v over the workgroup's kT threads, by a binary tree of fixed shape.
 DEV double block_sum(double v, double* sh) {
@@ -124,263 +127,25 @@ __global__ __launch_bounds__(kT) void k_train_gather(const LmConst* __restrict__
   }
 }
 
-__global__ __launch_bounds__(kT) void k_train_xv(const uint8_t* __restrict__ X, int64_t N, int Dp, int L,
-                                                 const double* __restrict__ v, double div,
-                                                 const double* __restrict__ a, double* __restrict__ out,
-                                                 double* __restrict__ out_a, const LmtCtl* ctl, int gate) {
-  if (gated(ctl, gate)) return;
-  extern __shared__ double sv[];  // VL doubles
-  for (int j = threadIdx.x; j <= Dp; j += kT) sv[j] = v[j];
-  __syncthreads();
-  const int gl = threadIdx.x & (L - 1);
-  // the group's kXvS consecutive samples: their loads are in flight together, and an entry of v is read once for all
-  const int64_t i0 = ((int64_t)blockIdx.x * (kT / L) + threadIdx.x / L) * kXvS;
-  const int ncg = Dp >> 4;
-  double acc[kXvS];
-#pragma unroll
-  for (int s = 0; s < kXvS; ++s) acc[s] = 0.0;
-  for (int g = gl; g < ncg; g += L) {
-    uint4 q[kXvS];
-#pragma unroll
-    for (int s = 0; s < kXvS; ++s)
-      q[s] = i0 + s < N ? reinterpret_cast<const uint4*>(X + (i0 + s) * Dp)[g] : make_uint4(0, 0, 0, 0);
-    const double* w = sv + 16 * g;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const double wk = w[k];
-#pragma unroll
-      for (int s = 0; s < kXvS; ++s) {
-        const uint32_t word = (k >> 2) == 0 ? q[s].x : (k >> 2) == 1 ? q[s].y : (k >> 2) == 2 ? q[s].z : q[s].w;
-        acc[s] += (double)((word >> (8 * (k & 3))) & 255u) * wk;
-      }
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < kXvS; ++s) {
-    double r = acc[s];
-    for (int o = L >> 1; o > 0; o >>= 1) r += __shfl_xor(r, o);
-    if (gl == 0 && i0 + s < N) {
-      const double z = r / div + sv[Dp];
-      out[i0 + s] = z;
-      if (a) out_a[i0 + s] = a[i0 + s] * z;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kT) void k_train_xt(const uint8_t* __restrict__ X, int64_t N, int Dp,
-                                                 const double* __restrict__ t, double* __restrict__ partial,
-                                                 const LmtCtl* ctl, int gate) {
-  if (gated(ctl, gate)) return;
-  __shared__ double red[16][kXtCols];
-  __shared__ double redb[16];
-  const int cgx = threadIdx.x & 15, sy = threadIdx.x >> 4;
-  const int g = blockIdx.x * 16 + cgx;  // column group of 16
-  const bool cols = g < (Dp >> 4);
-  const bool bias = blockIdx.x == 0 && cgx == 0;
-  const int64_t i0 = (int64_t)blockIdx.y * LMT_XT_BLOCK;
-  const int64_t i1 = i0 + LMT_XT_BLOCK < N ? i0 + LMT_XT_BLOCK : N;
-  double acc[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
-  double tb = 0.0;
-  if (cols || bias) {
-#pragma unroll 4
-    for (int64_t i = i0 + sy; i < i1; i += 16) {
-      const double ti = t[i];
-      if (bias) tb += ti;
-      if (cols) {
-        const uint4 q = *reinterpret_cast<const uint4*>(X + i * Dp + 16 * g);
-        const uint32_t word[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] += ti * (double)((word[k >> 2] >> (8 * (k & 3))) & 255u);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 16; ++k) red[sy][cgx * 16 + k] = acc[k];
-  if (bias) redb[sy] = tb;
-  __syncthreads();
-  const int VL = Dp + 1;
-  double* prow = partial + (int64_t)blockIdx.y * VL;
-  const int c = blockIdx.x * kXtCols + threadIdx.x;
-  if (c < Dp) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += red[q][threadIdx.x];
-    prow[c] = s;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    double s = 0.0;
-    for (int q = 0; q < 16; ++q) s += redb[q];
-    prow[Dp] = s;
-  }
-}
-
-__global__ __launch_bounds__(kT) void k_train_xt_reduce(const double* __restrict__ partial, int nblk, int Dp,
-                                                        const double* __restrict__ base, double* __restrict__ out,
-                                                        const LmtCtl* ctl, int gate) {
-  if (gated(ctl, gate)) return;
-  const int VL = Dp + 1;
-  const int j = blockIdx.x * kT + threadIdx.x;
-  if (j >= VL) return;
-  double s = 0.0;
-  for (int b = 0; b < nblk; ++b) s += partial[(int64_t)b * VL + j];
-  if (j < Dp) s = s / 255.0;
-  out[j] = base[j] + 2.0 * s;
-}
-
-__global__ __launch_bounds__(kT) void k_train_coef(const double* __restrict__ z, const int8_t* __restrict__ y, int64_t N,
-                                                   double c_pos, double c_neg, double* __restrict__ a,
-                                                   double* __restrict__ t, double* __restrict__ part_loss,
-                                                   double* __restrict__ part_act) {
-  __shared__ double sh[kT];
-  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-  double loss = 0.0, act = 0.0;
-  if (i < N) {
-    double ti;
-    const double ai = lmt_coef(y[i], z[i], c_pos, c_neg, &ti, &loss);
-    a[i] = ai;
-    t[i] = ti;
-    act = ai != 0.0 ? 1.0 : 0.0;
-  }
-  const double sl = block_sum(loss, sh);
-  const double sa = block_sum(act, sh);  // (counts below 2^53 are exact in a double)
-  if (threadIdx.x == 0) {
-    part_loss[blockIdx.x] = sl;
-    part_act[blockIdx.x] = sa;
-  }
-}
-
-// F and |grad F| at w from the parts; sets the flags; d = 0, r = p = -g.
-__global__ __launch_bounds__(kT) void k_train_eval(const double* __restrict__ w, const double* __restrict__ g, int VL,
-                                                   const double* __restrict__ part_loss,
-                                                   const double* __restrict__ part_act, int nb, double eps, int first,
-                                                   double* __restrict__ d, double* __restrict__ r,
-                                                   double* __restrict__ p, LmtCtl* ctl) {
-  __shared__ double sh[kT];
-  double ww = 0.0, gg = 0.0;
-  for (int j = threadIdx.x; j < VL; j += kT) {
-    ww += w[j] * w[j];
-    gg += g[j] * g[j];
-    d[j] = 0.0;
-    r[j] = -g[j];
-    p[j] = -g[j];
-  }
-  ww = block_sum(ww, sh);
-  gg = block_sum(gg, sh);
-  const double loss = block_sum_array(part_loss, nb, sh);
-  const double act = block_sum_array(part_act, nb, sh);
-  if (threadIdx.x == 0) {
-    const double gnorm = sqrt(gg);
-    const double g0 = first ? gnorm : ctl->gnorm0;
-    ctl->f = 0.5 * ww + loss;
-    ctl->gnorm = gnorm;
-    ctl->gnorm0 = g0;
-    ctl->rr = gg;
-    ctl->n_active = (int32_t)act;
-    ctl->converged = gnorm <= eps * g0 ? 1 : 0;
-    ctl->cg_done = ctl->converged;
-  }
-}
-
-// One CG step on (I + 2 X~_A^T C_A X~_A) d = -g with hp = H p already computed.
-__global__ __launch_bounds__(kT) void k_train_cg_update(double* __restrict__ d, double* __restrict__ r,
-                                                        double* __restrict__ p, const double* __restrict__ hp, int VL,
-                                                        LmtCtl* ctl) {
-  if (ctl->cg_done) return;
-  __shared__ double sh[kT];
-  const double rr = ctl->rr, gnorm = ctl->gnorm;
-  double a = 0.0;
-  for (int j = threadIdx.x; j < VL; j += kT) a += p[j] * hp[j];
-  const double php = block_sum(a, sh);  // >= |p|^2 > 0: H - I is positive semi-definite and r != 0
-  const double alpha = rr / php;
-  double b = 0.0;
-  for (int j = threadIdx.x; j < VL; j += kT) {
-    d[j] += alpha * p[j];
-    const double rj = r[j] - alpha * hp[j];
-    r[j] = rj;
-    b += rj * rj;
-  }
-  const double rr1 = block_sum(b, sh);
-  const double beta = rr1 / rr;
-  for (int j = threadIdx.x; j < VL; j += kT) p[j] = r[j] + beta * p[j];
-  if (threadIdx.x == 0) {
-    ctl->rr = rr1;
-    ctl->cg_iters += 1;
-    if (!(sqrt(rr1) > LMT_CG_TOL * gnorm)) ctl->cg_done = 1;
-  }
-}
-
-// Per block of kT samples, the change of their losses at every lambda = 2^-k.
-__global__ __launch_bounds__(kT) void k_train_ls_partials(const double* __restrict__ z, const double* __restrict__ xd,
-                                                          const int8_t* __restrict__ y, int64_t N, double c_pos,
-                                                          double c_neg, double* __restrict__ lspart,
-                                                          const LmtCtl* ctl) {
-  if (gated(ctl, GATE_CONVERGED)) return;
-  __shared__ double sh[kT];
-  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-  const bool valid = i < N;
-  const int yi = valid ? y[i] : 1;
-  const double zi = valid ? z[i] : 0.0, xi = valid ? xd[i] : 0.0;
-  double lambda = 1.0;
-  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
-    const double v = valid ? lmt_ls_delta(yi, zi, xi, lambda, c_pos, c_neg) : 0.0;
-    const double s = block_sum(v, sh);
-    if (threadIdx.x == 0) lspart[(int64_t)blockIdx.x * LMT_LS_STEPS + k] = s;
-  }
-}
-
-// The first lambda that satisfies Armijo; w += lambda d.
-__global__ __launch_bounds__(kT) void k_train_ls_pick(double* __restrict__ w, const double* __restrict__ g,
-                                                      const double* __restrict__ d, int VL,
-                                                      const double* __restrict__ lspart, int nb, LmtCtl* ctl) {
-  if (gated(ctl, GATE_CONVERGED)) return;
-  __shared__ double sh[kT];
-  double wd = 0.0, dd = 0.0, gd = 0.0;
-  for (int j = threadIdx.x; j < VL; j += kT) {
-    wd += w[j] * d[j];
-    dd += d[j] * d[j];
-    gd += g[j] * d[j];
-  }
-  wd = block_sum(wd, sh);
-  dd = block_sum(dd, sh);
-  gd = block_sum(gd, sh);
-  int picked = -1;  // (uniform: every thread sees the same sums)
-  double lambda = 1.0, step = 0.0;
-  for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nb; b += kT) a += lspart[(int64_t)b * LMT_LS_STEPS + k];
-    const double s = block_sum(a, sh);
-    const double delta = lambda * wd + 0.5 * lambda * lambda * dd + s;
-    if (picked < 0 && delta <= LMT_ARMIJO * lambda * gd) {
-      picked = k;
-      step = lambda;
-    }
-  }
-  if (picked >= 0)
-    for (int j = threadIdx.x; j < VL; j += kT) w[j] += step * d[j];
-  if (threadIdx.x == 0 && picked < 0) ctl->ls_fail = 1;
-}
-
-// ---- lm_train_solve_many: the kernels above for several problems on the same
-// samples.  A problem is its costs, its held-out group and its own LmtCtl; its
-// arrays lie `stride` doubles after its predecessor's.  The two matrix passes
-// take a block of pb problems (lmt_problem_block) per workgroup, block b of the
-// call along a grid dimension, and load and convert a 16-byte chunk once for
-// those of them that are live; the other kernels take one problem per
-// workgroup row.  Per problem every sum is the single kernel's, term for term.
-// A problem that is done (converged, or without a line-search step) is gated
-// everywhere, the evaluation included, so its arrays stay as lm_train_solve
-// would have left them at its break; a workgroup whose problems are all gated
-// returns at once, and one with fewer live problems than pb computes for 1, 2
-// or 4 of them.
+// ---- the solver, for the problems of a call on the same samples.  A problem
+// is its costs, its held-out group and its own LmtCtl; its arrays lie `stride`
+// doubles after its predecessor's (lm_train_core.h's LmtLayout).  The two
+// matrix passes take a block of pb problems (lmt_problem_block) per workgroup,
+// block b of the call along a grid dimension, and load and convert a 16-byte
+// chunk once for those of them that are live; the other kernels take one
+// problem per workgroup row.  Per problem every sum is the same, term for
+// term, whatever the company.  A problem that is done (converged, or without
+// a line-search step) is gated everywhere, the evaluation included, so its
+// arrays stay as a call of it alone leaves them when the host stops; a
+// workgroup whose problems are all gated returns at once, and one with fewer
+// live problems than pb computes for 1, 2 or 4 of them.
 
 struct LmtProb {  // a problem in device memory
   double c_pos, c_neg;
   int32_t held_out, pad;
 };
 
-struct LmtMany {
+struct LmtProblems {
   int n;  // problems of the call
   const LmtProb* prob;
   LmtCtl* ctl;
@@ -393,8 +158,9 @@ struct LmtMany {
 };
 enum { V_W = 0, V_G, V_D, V_R, V_P, V_HP };
 enum { S_Z = 0, S_U, S_A, S_T, S_AU, S_NONE = -1 };
+static_assert(V_HP + 1 == LMT_N_VEC && S_AU + 1 == LMT_N_SMP && kT == LMT_SAMPLE_BLOCK, "LmtLayout sizes these");
 
-DEV bool gated_many(const LmtCtl* ctl, int gate) {
+DEV bool gated(const LmtCtl* ctl, int gate) {
   return (gate == GATE_CG && (ctl->cg_done || ctl->ls_fail)) || (gate == GATE_CONVERGED && (ctl->converged || ctl->ls_fail));
 }
 
@@ -404,13 +170,13 @@ DEV bool gated_many(const LmtCtl* ctl, int gate) {
 struct LmtLive {
   int q[LMT_MANY_PB];
 };
-DEV int live_problems(const LmtMany& M, int q0, int pb, int gate, LmtLive& live) {
+DEV int live_problems(const LmtProblems& M, int q0, int pb, int gate, LmtLive& live) {
   int nl = 0;
 #pragma unroll
   for (int j = 0; j < LMT_MANY_PB; ++j) live.q[j] = q0;
 #pragma unroll
   for (int p = 0; p < LMT_MANY_PB; ++p) {
-    if (p < pb && q0 + p < M.n && !gated_many(M.ctl + q0 + p, gate)) {
+    if (p < pb && q0 + p < M.n && !gated(M.ctl + q0 + p, gate)) {
 #pragma unroll
       for (int j = 0; j < LMT_MANY_PB; ++j) live.q[j] = j == nl ? q0 + p : live.q[j];
       nl += 1;
@@ -421,12 +187,12 @@ DEV int live_problems(const LmtMany& M, int q0, int pb, int gate, LmtLive& live)
   return nl;
 }
 
-// k_train_xv for NP slots: slot p is live problem p (a slot past the nl live
+// k_train_xv with NP slots: slot p is live problem p (a slot past the nl live
 // ones computes on the first one's vector and writes nothing).  Entry 16 g + k
 // of slot p's vector is at sv[(k * ncg + g) * NP + p] (lanes of consecutive
 // chunks g read consecutive words), its bias at sv[Dp * NP + p].
 template <int NP>
-DEV void xv_many(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, const LmtMany& M, const LmtLive& live, int nl,
+DEV void xv_slots(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, const LmtProblems& M, const LmtLive& live, int nl,
                  int vi, double div, int ai, int oi, int oai, double* sv) {
   const int ncg = Dp >> 4, VL = Dp + 1;
 #pragma unroll
@@ -482,25 +248,25 @@ DEV void xv_many(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, const 
 
 // Sample array oi = X~ (vector vi) of the problems q0 .. q0 + pb - 1, q0 = pb
 // blockIdx.y; with ai, sample array oai = sample array ai times it.
-__global__ __launch_bounds__(kT) void k_train_xv_many(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, LmtMany M,
+__global__ __launch_bounds__(kT) void k_train_xv(const uint8_t* __restrict__ X, int64_t N, int Dp, int L, LmtProblems M,
                                                       int pb, int vi, double div, int ai, int oi, int oai, int gate) {
   LmtLive live;
   const int nl = live_problems(M, blockIdx.y * pb, pb, gate, live);
   if (nl == 0) return;
   extern __shared__ double sv[];  // pb x VL doubles
   if (nl == 1)
-    xv_many<1>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+    xv_slots<1>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
   else if (nl == 2)
-    xv_many<2>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+    xv_slots<2>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
   else
-    xv_many<4>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
+    xv_slots<4>(X, N, Dp, L, M, live, nl, vi, div, ai, oi, oai, sv);
 }
 
-// k_train_xt for NP slots (as xv_many's): the block's sums of X^T t of each,
+// k_train_xt with NP slots (as xv_slots'): the block's sums of X^T t of each,
 // t = the problem's sample array ti.  A chunk is loaded and converted once;
 // the 16 sample lanes are added through LDS one problem after the other.
 template <int NP>
-DEV void xt_many(const uint8_t* __restrict__ X, int64_t N, int Dp, const LmtMany& M, const LmtLive& live, int nl, int ti,
+DEV void xt_slots(const uint8_t* __restrict__ X, int64_t N, int Dp, const LmtProblems& M, const LmtLive& live, int nl, int ti,
                  double (*red)[kXtCols], double* redb) {
   const int cgx = threadIdx.x & 15, sy = threadIdx.x >> 4;
   const int g = blockIdx.x * 16 + cgx;  // column group of 16
@@ -565,7 +331,7 @@ DEV void xt_many(const uint8_t* __restrict__ X, int64_t N, int Dp, const LmtMany
 }
 
 // The blocks' sums of X^T (sample array ti) of the problems q0 .. q0 + pb - 1, q0 = pb blockIdx.z.
-__global__ __launch_bounds__(kT) void k_train_xt_many(const uint8_t* __restrict__ X, int64_t N, int Dp, LmtMany M, int pb,
+__global__ __launch_bounds__(kT) void k_train_xt(const uint8_t* __restrict__ X, int64_t N, int Dp, LmtProblems M, int pb,
                                                       int ti, int gate) {
   LmtLive live;
   const int nl = live_problems(M, blockIdx.z * pb, pb, gate, live);
@@ -573,19 +339,19 @@ __global__ __launch_bounds__(kT) void k_train_xt_many(const uint8_t* __restrict_
   __shared__ double red[16][kXtCols];
   __shared__ double redb[16];
   if (nl == 1)
-    xt_many<1>(X, N, Dp, M, live, nl, ti, red, redb);
+    xt_slots<1>(X, N, Dp, M, live, nl, ti, red, redb);
   else if (nl == 2)
-    xt_many<2>(X, N, Dp, M, live, nl, ti, red, redb);
+    xt_slots<2>(X, N, Dp, M, live, nl, ti, red, redb);
   else
-    xt_many<4>(X, N, Dp, M, live, nl, ti, red, redb);
+    xt_slots<4>(X, N, Dp, M, live, nl, ti, red, redb);
 }
 
 // From here on blockIdx.y is the problem.
 
 // vector oi = vector bi + 2 X~^T t from the blocks' sums, in index order
-__global__ __launch_bounds__(kT) void k_train_xt_reduce_many(LmtMany M, int nblk, int Dp, int bi, int oi, int gate) {
+__global__ __launch_bounds__(kT) void k_train_xt_reduce(LmtProblems M, int nblk, int Dp, int bi, int oi, int gate) {
   const int q = blockIdx.y;
-  if (gated_many(M.ctl + q, gate)) return;
+  if (gated(M.ctl + q, gate)) return;
   const int VL = Dp + 1;
   const int j = blockIdx.x * kT + threadIdx.x;
   if (j >= VL) return;
@@ -597,9 +363,10 @@ __global__ __launch_bounds__(kT) void k_train_xt_reduce_many(LmtMany M, int nblk
   vec[(int64_t)oi * VL + j] = vec[(int64_t)bi * VL + j] + 2.0 * s;
 }
 
-__global__ __launch_bounds__(kT) void k_train_coef_many(LmtMany M, const int8_t* __restrict__ y, int64_t N, int nb) {
+// Per sample: its cost (none for a held-out one), active cost, gradient coefficient and loss; the block's sums.
+__global__ __launch_bounds__(kT) void k_train_coef(LmtProblems M, const int8_t* __restrict__ y, int64_t N, int nb) {
   const int q = blockIdx.y;
-  if (gated_many(M.ctl + q, GATE_CONVERGED)) return;
+  if (gated(M.ctl + q, GATE_CONVERGED)) return;
   __shared__ double sh[kT];
   const LmtProb pr = M.prob[q];
   double* smp = M.smp + (int64_t)q * M.smp_stride;
@@ -614,7 +381,7 @@ __global__ __launch_bounds__(kT) void k_train_coef_many(LmtMany M, const int8_t*
     act = ai != 0.0 ? 1.0 : 0.0;
   }
   const double sl = block_sum(loss, sh);
-  const double sa = block_sum(act, sh);
+  const double sa = block_sum(act, sh);  // (counts below 2^53 are exact in a double)
   if (threadIdx.x == 0) {
     double* part = M.part + (int64_t)q * M.part_stride;
     part[blockIdx.x] = sl;
@@ -622,10 +389,11 @@ __global__ __launch_bounds__(kT) void k_train_coef_many(LmtMany M, const int8_t*
   }
 }
 
-__global__ __launch_bounds__(kT) void k_train_eval_many(LmtMany M, int VL, int nb, double eps, int first) {
+// F and |grad F| at w from the parts; sets the flags; d = 0, r = p = -g.
+__global__ __launch_bounds__(kT) void k_train_eval(LmtProblems M, int VL, int nb, double eps, int first) {
   const int q = blockIdx.x;
   LmtCtl* ctl = M.ctl + q;
-  if (gated_many(ctl, GATE_CONVERGED)) return;
+  if (gated(ctl, GATE_CONVERGED)) return;
   __shared__ double sh[kT];
   double* vec = M.vec + (int64_t)q * M.vec_stride;
   const double *w = vec + (int64_t)V_W * VL, *g = vec + (int64_t)V_G * VL;
@@ -656,10 +424,11 @@ __global__ __launch_bounds__(kT) void k_train_eval_many(LmtMany M, int VL, int n
   }
 }
 
-__global__ __launch_bounds__(kT) void k_train_cg_update_many(LmtMany M, int VL) {
+// One CG step on (I + 2 X~_A^T C_A X~_A) d = -g with hp = H p already computed.
+__global__ __launch_bounds__(kT) void k_train_cg_update(LmtProblems M, int VL) {
   const int q = blockIdx.x;
   LmtCtl* ctl = M.ctl + q;
-  if (gated_many(ctl, GATE_CG)) return;
+  if (gated(ctl, GATE_CG)) return;
   __shared__ double sh[kT];
   double* vec = M.vec + (int64_t)q * M.vec_stride;
   double *d = vec + (int64_t)V_D * VL, *r = vec + (int64_t)V_R * VL, *p = vec + (int64_t)V_P * VL;
@@ -667,7 +436,7 @@ __global__ __launch_bounds__(kT) void k_train_cg_update_many(LmtMany M, int VL) 
   const double rr = ctl->rr, gnorm = ctl->gnorm;
   double a = 0.0;
   for (int j = threadIdx.x; j < VL; j += kT) a += p[j] * hp[j];
-  const double php = block_sum(a, sh);
+  const double php = block_sum(a, sh);  // >= |p|^2 > 0: H - I is positive semi-definite and r != 0
   const double alpha = rr / php;
   double b = 0.0;
   for (int j = threadIdx.x; j < VL; j += kT) {
@@ -686,10 +455,11 @@ __global__ __launch_bounds__(kT) void k_train_cg_update_many(LmtMany M, int VL) 
   }
 }
 
-__global__ __launch_bounds__(kT) void k_train_ls_partials_many(LmtMany M, const int8_t* __restrict__ y, int64_t N,
+// Per block of kT samples, the change of their losses at every lambda = 2^-k.
+__global__ __launch_bounds__(kT) void k_train_ls_partials(LmtProblems M, const int8_t* __restrict__ y, int64_t N,
                                                                int nb) {
   const int q = blockIdx.y;
-  if (gated_many(M.ctl + q, GATE_CONVERGED)) return;
+  if (gated(M.ctl + q, GATE_CONVERGED)) return;
   __shared__ double sh[kT];
   const LmtProb pr = M.prob[q];
   const double* smp = M.smp + (int64_t)q * M.smp_stride;
@@ -707,10 +477,11 @@ __global__ __launch_bounds__(kT) void k_train_ls_partials_many(LmtMany M, const 
   }
 }
 
-__global__ __launch_bounds__(kT) void k_train_ls_pick_many(LmtMany M, int VL, int nb) {
+// The first lambda that satisfies Armijo; w += lambda d.
+__global__ __launch_bounds__(kT) void k_train_ls_pick(LmtProblems M, int VL, int nb) {
   const int q = blockIdx.x;
   LmtCtl* ctl = M.ctl + q;
-  if (gated_many(ctl, GATE_CONVERGED)) return;
+  if (gated(ctl, GATE_CONVERGED)) return;
   __shared__ double sh[kT];
   double* vec = M.vec + (int64_t)q * M.vec_stride;
   double* w = vec + (int64_t)V_W * VL;
@@ -725,7 +496,7 @@ __global__ __launch_bounds__(kT) void k_train_ls_pick_many(LmtMany M, int VL, in
   wd = block_sum(wd, sh);
   dd = block_sum(dd, sh);
   gd = block_sum(gd, sh);
-  int picked = -1;
+  int picked = -1;  // (uniform: every thread sees the same sums)
   double lambda = 1.0, step = 0.0;
   for (int k = 0; k < LMT_LS_STEPS; ++k, lambda *= 0.5) {
     double a = 0.0;
@@ -745,7 +516,7 @@ __global__ __launch_bounds__(kT) void k_train_ls_pick_many(LmtMany M, int VL, in
 // Per block of kT samples and problem, the held-out group's samples by label
 // and those on the wrong side of z, the margins of the last evaluation:
 // counts[(q * nb + block) * 4 + (n_pos, n_neg, miss_pos, miss_neg)].
-__global__ __launch_bounds__(kT) void k_train_heldout(LmtMany M, const int8_t* __restrict__ y, int64_t N, int nb,
+__global__ __launch_bounds__(kT) void k_train_heldout(LmtProblems M, const int8_t* __restrict__ y, int64_t N, int nb,
                                                       int32_t* __restrict__ counts) {
   const int q = blockIdx.y;
   __shared__ int32_t sh[4][kT];
@@ -785,24 +556,16 @@ struct lm_train_ctx {
   DevBuf<uint8_t> X;
   DevBuf<int8_t> y;
   std::vector<int8_t> h_y;
-  // solver (sized at the first solve for the samples then stored)
-  DevBuf<double> vec;   // w, g, d, r, p, hp: 6 x VL
-  DevBuf<double> smp;   // z, u, a, t, au: 5 x cap_n
-  DevBuf<double> part;  // part_loss, part_act (nb each), lspart (nb x LMT_LS_STEPS)
-  DevBuf<double> xtp;   // k_train_xt's partials, nblk x VL
-  int64_t cap_n = 0;
-  DevBuf<LmtCtl> ctl;
-  HostBuf<LmtCtl> h_ctl;
-  HostBuf<double> h_vec;  // VL
-  // groups (lm_train_set_groups) and the arrays of lm_train_solve_many, sized per call
+  // groups (lm_train_set_groups)
   bool groups_set = false;
   std::vector<uint8_t> h_group;
   DevBuf<uint8_t> group;  // max_samples; all 0 while no groups are set (no problem holds a group out then)
-  DevBuf<double> m_vec, m_smp, m_part, m_xtp;
-  DevBuf<LmtProb> m_prob;
-  DevBuf<LmtCtl> m_ctl;
-  DevBuf<int32_t> m_counts;
-  HostBuf<LmtCtl> h_m_ctl;  // LM_TRAIN_MAX_PROBLEMS
+  // solver: the arrays of a call's problems (LmtProblems), sized per call by bind_problems
+  DevBuf<double> vec, smp, part, xtp;
+  DevBuf<int32_t> counts;
+  DevBuf<LmtProb> prob;   // LM_TRAIN_MAX_PROBLEMS, as ctl and h_ctl
+  DevBuf<LmtCtl> ctl;
+  HostBuf<LmtCtl> h_ctl;
   // gather
   DevBuf<uint8_t> stage, luts;
   DevBuf<unsigned> mm;
@@ -824,41 +587,6 @@ int lanes_per_sample(int Dp) {
   int L = 1;
   while (L < ncg && L < 64) L <<= 1;
   return L;
-}
-
-void launch_xv(lm_train_ctx* c, const double* v, double div, const double* a, double* out, double* out_a, int gate) {
-  const int L = lanes_per_sample(c->Dp);
-  const int spb = kT / L * kXvS;
-  const unsigned grid = (unsigned)((c->n + spb - 1) / spb);
-  hipLaunchKernelGGL(k_train_xv, dim3(grid), dim3(kT), sizeof(double) * (size_t)c->VL, c->stream, c->X.p, c->n, c->Dp, L,
-                     v, div, a, out, out_a, c->ctl.p, gate);
-}
-
-// out = base + 2 X~^T t
-void launch_xt(lm_train_ctx* c, const double* t, const double* base, double* out, int gate) {
-  const int nblk = (int)((c->n + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
-  const int nchunk = ((c->Dp >> 4) + 15) / 16;
-  hipLaunchKernelGGL(k_train_xt, dim3(nchunk, nblk), dim3(kT), 0, c->stream, c->X.p, c->n, c->Dp, t, c->xtp.p, c->ctl.p,
-                     gate);
-  hipLaunchKernelGGL(k_train_xt_reduce, dim3((c->VL + kT - 1) / kT), dim3(kT), 0, c->stream, c->xtp.p, nblk, c->Dp, base,
-                     out, c->ctl.p, gate);
-}
-
-void size_solver(lm_train_ctx* c) {
-  if (!c->vec.p) {
-    c->vec.alloc(6 * (size_t)c->VL);
-    c->ctl.alloc(1);
-    c->h_ctl.alloc(1);
-    c->h_vec.alloc((size_t)c->VL);
-  }
-  if (c->cap_n < c->n) {
-    const size_t nb = (size_t)((c->n + kT - 1) / kT);
-    const size_t nblk = (size_t)((c->n + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
-    c->smp.alloc(5 * (size_t)c->n);
-    c->part.alloc(nb * (2 + LMT_LS_STEPS));
-    c->xtp.alloc(nblk * (size_t)c->VL);
-    c->cap_n = c->n;
-  }
 }
 
 void check_add(const lm_train_ctx* c, int64_t n) {
@@ -1027,92 +755,27 @@ LM_API lm_status lm_train_patches(lm_train_ctx* ctx, int32_t first, int32_t n, u
   });
 }
 
-LM_API lm_status lm_train_solve(lm_train_ctx* ctx, double c_pos, double c_neg, double eps, int32_t max_iter,
-                                double* out_W, double* out_rho, lm_train_stats* stats) {
-  if (!ctx || !out_W || !out_rho) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
-  if (!(c_pos > 0.0) || !std::isfinite(c_pos) || !(c_neg > 0.0) || !std::isfinite(c_neg))
-    return fail(LM_ERR_INVALID_ARGUMENT, "c_pos and c_neg must be positive and finite");
-  if (!(eps > 0.0) || !std::isfinite(eps)) return fail(LM_ERR_INVALID_ARGUMENT, "eps must be positive and finite");
-  if (max_iter < 0) return fail(LM_ERR_INVALID_ARGUMENT, "max_iter is negative");
-  if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
-  return guarded([&] {
-    lm_train_ctx* c = ctx;
-    HIPCHK(hipSetDevice(c->device));
-    size_solver(c);
-    const int VL = c->VL;
-    const int64_t N = c->n;
-    double *w = c->vec.p, *g = w + VL, *d = g + VL, *r = d + VL, *p = r + VL, *hp = p + VL;
-    double *z = c->smp.p, *u = z + N, *a = u + N, *t = a + N, *au = t + N;
-    const int nb = (int)((N + kT - 1) / kT);
-    double *part_loss = c->part.p, *part_act = part_loss + nb, *lspart = part_act + nb;
-    // CG steps enqueued per outer iteration: in exact arithmetic CG ends within
-    // VL steps; past the cap the step taken is that of a shorter CG run
-    const int cg_cap = c->D + 1 < 96 ? c->D + 1 : 96;
-    HIPCHK(hipMemsetAsync(w, 0, sizeof(double) * 6 * (size_t)VL, c->stream));
-    HIPCHK(hipMemsetAsync(c->ctl.p, 0, sizeof(LmtCtl), c->stream));
-    int it = 0;
-    for (;; ++it) {
-      // F, grad F and the active set at w
-      launch_xv(c, w, 255.0, nullptr, z, nullptr, GATE_NONE);
-      hipLaunchKernelGGL(k_train_coef, dim3(nb), dim3(kT), 0, c->stream, z, c->y.p, N, c_pos, c_neg, a, t, part_loss,
-                         part_act);
-      launch_xt(c, t, w, g, GATE_NONE);
-      hipLaunchKernelGGL(k_train_eval, dim3(1), dim3(kT), 0, c->stream, w, g, VL, part_loss, part_act, nb, eps,
-                         it == 0 ? 1 : 0, d, r, p, c->ctl.p);
-      if (it < max_iter) {
-        for (int k = 0; k < cg_cap; ++k) {
-          launch_xv(c, p, 255.0, a, u, au, GATE_CG);
-          launch_xt(c, au, p, hp, GATE_CG);
-          hipLaunchKernelGGL(k_train_cg_update, dim3(1), dim3(kT), 0, c->stream, d, r, p, hp, VL, c->ctl.p);
-        }
-        launch_xv(c, d, 255.0, nullptr, u, nullptr, GATE_CONVERGED);
-        hipLaunchKernelGGL(k_train_ls_partials, dim3(nb), dim3(kT), 0, c->stream, z, u, c->y.p, N, c_pos, c_neg, lspart,
-                           c->ctl.p);
-        hipLaunchKernelGGL(k_train_ls_pick, dim3(1), dim3(kT), 0, c->stream, w, g, d, VL, lspart, nb, c->ctl.p);
-      }
-      HIPCHK(hipGetLastError());
-      COPY_SYNC(c->h_ctl.p, c->ctl.p, sizeof(LmtCtl), hipMemcpyDeviceToHost, c->stream);
-      if (c->h_ctl.p->converged || c->h_ctl.p->ls_fail || it >= max_iter) break;
-    }
-    const LmtCtl& R = *c->h_ctl.p;
-    if (R.ls_fail && !R.converged) {  // w is unchanged since the evaluation: the figures are its
-      g_err = "the line search found no step";
-    }
-    COPY_SYNC(c->h_vec.p, w, sizeof(double) * (size_t)VL, hipMemcpyDeviceToHost, c->stream);
-    for (int j = 0; j < c->D; ++j) out_W[j] = c->h_vec.p[j] / 255.0;
-    *out_rho = -c->h_vec.p[c->Dp];
-    if (stats) {
-      stats->objective = R.f;
-      stats->grad_norm = R.gnorm;
-      stats->grad_norm0 = R.gnorm0;
-      stats->outer_iters = it;
-      stats->cg_iters = R.cg_iters;
-      stats->converged = R.converged;
-      stats->n_active = R.n_active;
-    }
-  });
-}
-
 namespace {
 
-void launch_xv_many(lm_train_ctx* c, const LmtMany& M, int vi, int ai, int oi, int oai, int gate) {
+// sample array oi = X~ (vector vi) with the matrix' bytes over div; with ai, sample array oai = sample array ai times it
+void launch_xv(lm_train_ctx* c, const LmtProblems& M, int vi, double div, int ai, int oi, int oai, int gate) {
   const int L = lanes_per_sample(c->Dp);
   const int spb = kT / L * kXvS;
   const int pb = lmt_problem_block(c->D);
   const dim3 grid((unsigned)((c->n + spb - 1) / spb), (unsigned)((M.n + pb - 1) / pb));
   const size_t lds = sizeof(double) * (size_t)pb * (size_t)c->VL;
-  hipLaunchKernelGGL(k_train_xv_many, grid, dim3(kT), lds, c->stream, c->X.p, c->n, c->Dp, L, M, pb, vi, 255.0, ai, oi, oai,
+  hipLaunchKernelGGL(k_train_xv, grid, dim3(kT), lds, c->stream, c->X.p, c->n, c->Dp, L, M, pb, vi, div, ai, oi, oai,
                      gate);
 }
 
 // vector oi = vector bi + 2 X~^T (sample array ti), per problem
-void launch_xt_many(lm_train_ctx* c, const LmtMany& M, int ti, int bi, int oi, int gate) {
+void launch_xt(lm_train_ctx* c, const LmtProblems& M, int ti, int bi, int oi, int gate) {
   const int nblk = (int)((c->n + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
   const int nchunk = ((c->Dp >> 4) + 15) / 16;
   const int pb = lmt_problem_block(c->D);
   const dim3 grid(nchunk, nblk, (M.n + pb - 1) / pb);
-  hipLaunchKernelGGL(k_train_xt_many, grid, dim3(kT), 0, c->stream, c->X.p, c->n, c->Dp, M, pb, ti, gate);
-  hipLaunchKernelGGL(k_train_xt_reduce_many, dim3((c->VL + kT - 1) / kT, M.n), dim3(kT), 0, c->stream, M, nblk, c->Dp,
+  hipLaunchKernelGGL(k_train_xt, grid, dim3(kT), 0, c->stream, c->X.p, c->n, c->Dp, M, pb, ti, gate);
+  hipLaunchKernelGGL(k_train_xt_reduce, dim3((c->VL + kT - 1) / kT, M.n), dim3(kT), 0, c->stream, M, nblk, c->Dp,
                      bi, oi, gate);
 }
 
@@ -1144,6 +807,149 @@ std::string refuse_problems(const lm_train_ctx* c, const lm_train_problem* pr, i
     if (in_group[(size_t)pr[q].held_out] == c->n) return at + "its held-out group holds every stored sample";
   }
   return "";
+}
+
+// ---- a solve, step by step (solve_problems below)
+
+// The arrays of a call of P problems on the stored samples: grown where they are too small, and bound.
+LmtProblems bind_problems(lm_train_ctx* c, int P) {
+  size_groups(c);
+  const LmtLayout L = lmt_layout(c->n, c->VL);
+  auto size = [P](auto& b, int64_t per_problem) {
+    if (b.n < (size_t)P * (size_t)per_problem) b.alloc((size_t)P * (size_t)per_problem);
+  };
+  size(c->vec, L.vec);
+  size(c->smp, L.smp);
+  size(c->part, L.part);
+  size(c->xtp, L.xtp);
+  size(c->counts, L.counts);
+  if (!c->prob.p) {
+    c->prob.alloc(LM_TRAIN_MAX_PROBLEMS);
+    c->ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
+    c->h_ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
+  }
+  LmtProblems M;
+  M.n = P;
+  M.prob = c->prob.p;
+  M.ctl = c->ctl.p;
+  M.group = c->group.p;
+  M.vec = c->vec.p;
+  M.smp = c->smp.p;
+  M.part = c->part.p;
+  M.xtp = c->xtp.p;
+  M.vec_stride = L.vec;
+  M.smp_stride = L.smp;
+  M.part_stride = L.part;
+  M.xtp_stride = L.xtp;
+  return M;
+}
+
+// The problems into device memory; each starts at w = 0 with a cleared control block.
+void upload_problems(lm_train_ctx* c, const LmtProblems& M, const lm_train_problem* problems) {
+  std::vector<LmtProb> pr((size_t)M.n);
+  for (int q = 0; q < M.n; ++q) pr[(size_t)q] = LmtProb{problems[q].c_pos, problems[q].c_neg, problems[q].held_out, 0};
+  COPY_SYNC(c->prob.p, pr.data(), sizeof(LmtProb) * pr.size(), hipMemcpyHostToDevice, c->stream);
+  HIPCHK(hipMemsetAsync(M.vec, 0, sizeof(double) * (size_t)M.n * (size_t)M.vec_stride, c->stream));
+  HIPCHK(hipMemsetAsync(M.ctl, 0, sizeof(LmtCtl) * (size_t)M.n, c->stream));
+}
+
+// One outer iteration of the problems that are not done: F, grad F and the
+// active set at w; then, with `step`, the CG run and the line search.
+void enqueue_outer(lm_train_ctx* c, const LmtProblems& M, double eps, bool first, bool step) {
+  const int VL = c->VL, P = M.n;
+  const int64_t N = c->n;
+  const int nb = (int)lmt_layout(N, VL).nb;
+  // CG steps enqueued per outer iteration: in exact arithmetic CG ends within
+  // VL steps; past the cap the step taken is that of a shorter CG run
+  const int cg_cap = c->D + 1 < 96 ? c->D + 1 : 96;
+  launch_xv(c, M, V_W, 255.0, S_NONE, S_Z, S_NONE, GATE_CONVERGED);
+  hipLaunchKernelGGL(k_train_coef, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
+  launch_xt(c, M, S_T, V_W, V_G, GATE_CONVERGED);
+  hipLaunchKernelGGL(k_train_eval, dim3(P), dim3(kT), 0, c->stream, M, VL, nb, eps, first ? 1 : 0);
+  if (step) {
+    for (int k = 0; k < cg_cap; ++k) {
+      launch_xv(c, M, V_P, 255.0, S_A, S_U, S_AU, GATE_CG);
+      launch_xt(c, M, S_AU, V_P, V_HP, GATE_CG);
+      hipLaunchKernelGGL(k_train_cg_update, dim3(P), dim3(kT), 0, c->stream, M, VL);
+    }
+    launch_xv(c, M, V_D, 255.0, S_NONE, S_U, S_NONE, GATE_CONVERGED);
+    hipLaunchKernelGGL(k_train_ls_partials, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
+    hipLaunchKernelGGL(k_train_ls_pick, dim3(P), dim3(kT), 0, c->stream, M, VL, nb);
+  }
+  HIPCHK(hipGetLastError());
+}
+
+// The control blocks after outer iteration `it`, in c->h_ctl; a problem that
+// is done now (converged, without a line-search step, or at max_iter) gets
+// outer[q] = it.  True when every problem is done.
+bool read_controls(lm_train_ctx* c, const LmtProblems& M, int it, int max_iter, std::vector<int>& outer) {
+  COPY_SYNC(c->h_ctl.p, M.ctl, sizeof(LmtCtl) * (size_t)M.n, hipMemcpyDeviceToHost, c->stream);
+  const LmtCtl* R = c->h_ctl.p;
+  bool all = true;
+  for (int q = 0; q < M.n; ++q) {
+    if (outer[(size_t)q] < 0 && (R[q].converged || R[q].ls_fail || it >= max_iter)) outer[(size_t)q] = it;
+    all = all && outer[(size_t)q] >= 0;
+  }
+  return all;
+}
+
+// The weights, the stats (from c->h_ctl) and, with `heldout`, the held-out
+// counts of every problem.  A problem whose line search found no step is
+// named in g_err, by its number when `numbered`; its w is unchanged since the
+// evaluation, so the figures are its.
+void read_results(lm_train_ctx* c, const LmtProblems& M, const std::vector<int>& outer, bool numbered, double* out_W,
+                  double* out_rho, lm_train_stats* stats, lm_train_heldout* heldout) {
+  const int VL = c->VL, P = M.n;
+  const int nb = (int)lmt_layout(c->n, VL).nb;
+  std::vector<int32_t> counts;
+  if (heldout) {
+    hipLaunchKernelGGL(k_train_heldout, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, c->n, nb, c->counts.p);
+    HIPCHK(hipGetLastError());
+    counts.resize((size_t)P * (size_t)nb * 4);
+    COPY_SYNC(counts.data(), c->counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, c->stream);
+  }
+  std::vector<double> w((size_t)P * (size_t)VL);
+  HIPCHK(hipMemcpy2DAsync(w.data(), sizeof(double) * (size_t)VL, M.vec, sizeof(double) * (size_t)M.vec_stride,
+                          sizeof(double) * (size_t)VL, (size_t)P, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const LmtCtl* R = c->h_ctl.p;
+  for (int q = 0; q < P; ++q) {
+    const double* wq = w.data() + (size_t)q * (size_t)VL;
+    for (int j = 0; j < c->D; ++j) out_W[(size_t)q * (size_t)c->D + (size_t)j] = wq[j] / 255.0;
+    out_rho[q] = -wq[c->Dp];
+    if (R[q].ls_fail && !R[q].converged)
+      g_err = "the line search found no step" + (numbered ? " (problem " + std::to_string(q) + ")" : std::string());
+    if (stats) {
+      stats[q].objective = R[q].f;
+      stats[q].grad_norm = R[q].gnorm;
+      stats[q].grad_norm0 = R[q].gnorm0;
+      stats[q].outer_iters = outer[(size_t)q];
+      stats[q].cg_iters = R[q].cg_iters;
+      stats[q].converged = R[q].converged;
+      stats[q].n_active = R[q].n_active;
+    }
+    if (heldout) {
+      int32_t s[4] = {0, 0, 0, 0};
+      for (int b = 0; b < nb; ++b)  // in block order
+        for (int k = 0; k < 4; ++k) s[k] += counts[((size_t)q * (size_t)nb + (size_t)b) * 4 + (size_t)k];
+      heldout[q] = lm_train_heldout{s[0], s[1], s[2], s[3]};
+    }
+  }
+}
+
+// The solver: P checked problems on the stored samples.  The host reads the
+// control blocks once per outer iteration and stops when every problem is done.
+void solve_problems(lm_train_ctx* c, const lm_train_problem* problems, int P, double eps, int max_iter, bool numbered,
+                    double* out_W, double* out_rho, lm_train_stats* stats, lm_train_heldout* heldout) {
+  HIPCHK(hipSetDevice(c->device));
+  const LmtProblems M = bind_problems(c, P);
+  upload_problems(c, M, problems);
+  std::vector<int> outer((size_t)P, -1);  // a problem's outer iterations, once it is done
+  for (int it = 0;; ++it) {
+    enqueue_outer(c, M, eps, it == 0, it < max_iter);
+    if (read_controls(c, M, it, max_iter, outer)) break;
+  }
+  read_results(c, M, outer, numbered, out_W, out_rho, stats, heldout);
 }
 
 }  // namespace
@@ -1180,121 +986,39 @@ LM_API lm_status lm_train_solve_many(lm_train_ctx* ctx, const lm_train_problem* 
   if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
   const std::string why = refuse_problems(ctx, problems, n_problems);
   if (!why.empty()) return fail(LM_ERR_INVALID_ARGUMENT, why);
+  return guarded([&] { solve_problems(ctx, problems, n_problems, eps, max_iter, true, out_W, out_rho, stats, heldout); });
+}
+
+// The one-problem call {c_pos, c_neg, no held-out group}, with its own refusals.
+LM_API lm_status lm_train_solve(lm_train_ctx* ctx, double c_pos, double c_neg, double eps, int32_t max_iter,
+                                double* out_W, double* out_rho, lm_train_stats* stats) {
+  if (!ctx || !out_W || !out_rho) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(c_pos > 0.0) || !std::isfinite(c_pos) || !(c_neg > 0.0) || !std::isfinite(c_neg))
+    return fail(LM_ERR_INVALID_ARGUMENT, "c_pos and c_neg must be positive and finite");
+  if (!(eps > 0.0) || !std::isfinite(eps)) return fail(LM_ERR_INVALID_ARGUMENT, "eps must be positive and finite");
+  if (max_iter < 0) return fail(LM_ERR_INVALID_ARGUMENT, "max_iter is negative");
+  if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
   return guarded([&] {
-    lm_train_ctx* c = ctx;
-    HIPCHK(hipSetDevice(c->device));
-    size_groups(c);
-    const int VL = c->VL, P = n_problems;
-    const int64_t N = c->n;
-    const int nb = (int)((N + kT - 1) / kT);
-    const int nblk = (int)((N + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK);
-    LmtMany M;
-    M.n = P;
-    M.vec_stride = 6 * (int64_t)VL;
-    M.smp_stride = 5 * N;
-    M.part_stride = (int64_t)nb * (2 + LMT_LS_STEPS);
-    M.xtp_stride = (int64_t)nblk * VL;
-    auto size = [](DevBuf<double>& b, size_t n) {
-      if (b.n < n) b.alloc(n);
-    };
-    size(c->m_vec, (size_t)P * (size_t)M.vec_stride);
-    size(c->m_smp, (size_t)P * (size_t)M.smp_stride);
-    size(c->m_part, (size_t)P * (size_t)M.part_stride);
-    size(c->m_xtp, (size_t)P * (size_t)M.xtp_stride);
-    if (c->m_counts.n < (size_t)P * (size_t)nb * 4) c->m_counts.alloc((size_t)P * (size_t)nb * 4);
-    if (!c->m_prob.p) {
-      c->m_prob.alloc(LM_TRAIN_MAX_PROBLEMS);
-      c->m_ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
-      c->h_m_ctl.alloc(LM_TRAIN_MAX_PROBLEMS);
-    }
-    M.prob = c->m_prob.p;
-    M.ctl = c->m_ctl.p;
-    M.group = c->group.p;
-    M.vec = c->m_vec.p;
-    M.smp = c->m_smp.p;
-    M.part = c->m_part.p;
-    M.xtp = c->m_xtp.p;
-    std::vector<LmtProb> pr((size_t)P);
-    for (int q = 0; q < P; ++q) pr[(size_t)q] = LmtProb{problems[q].c_pos, problems[q].c_neg, problems[q].held_out, 0};
-    COPY_SYNC(c->m_prob.p, pr.data(), sizeof(LmtProb) * (size_t)P, hipMemcpyHostToDevice, c->stream);
-    const int cg_cap = c->D + 1 < 96 ? c->D + 1 : 96;
-    HIPCHK(hipMemsetAsync(M.vec, 0, sizeof(double) * (size_t)P * (size_t)M.vec_stride, c->stream));
-    HIPCHK(hipMemsetAsync(M.ctl, 0, sizeof(LmtCtl) * (size_t)P, c->stream));
-    std::vector<int> outer((size_t)P, -1);  // a problem's outer iterations, once it is done
-    const LmtCtl* R = c->h_m_ctl.p;
-    for (int it = 0;; ++it) {
-      launch_xv_many(c, M, V_W, S_NONE, S_Z, S_NONE, GATE_CONVERGED);
-      hipLaunchKernelGGL(k_train_coef_many, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
-      launch_xt_many(c, M, S_T, V_W, V_G, GATE_CONVERGED);
-      hipLaunchKernelGGL(k_train_eval_many, dim3(P), dim3(kT), 0, c->stream, M, VL, nb, eps, it == 0 ? 1 : 0);
-      if (it < max_iter) {
-        for (int k = 0; k < cg_cap; ++k) {
-          launch_xv_many(c, M, V_P, S_A, S_U, S_AU, GATE_CG);
-          launch_xt_many(c, M, S_AU, V_P, V_HP, GATE_CG);
-          hipLaunchKernelGGL(k_train_cg_update_many, dim3(P), dim3(kT), 0, c->stream, M, VL);
-        }
-        launch_xv_many(c, M, V_D, S_NONE, S_U, S_NONE, GATE_CONVERGED);
-        hipLaunchKernelGGL(k_train_ls_partials_many, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb);
-        hipLaunchKernelGGL(k_train_ls_pick_many, dim3(P), dim3(kT), 0, c->stream, M, VL, nb);
-      }
-      HIPCHK(hipGetLastError());
-      COPY_SYNC(c->h_m_ctl.p, M.ctl, sizeof(LmtCtl) * (size_t)P, hipMemcpyDeviceToHost, c->stream);
-      bool all = true;
-      for (int q = 0; q < P; ++q) {
-        if (outer[(size_t)q] < 0 && (R[q].converged || R[q].ls_fail || it >= max_iter)) outer[(size_t)q] = it;
-        all = all && outer[(size_t)q] >= 0;
-      }
-      if (all) break;
-    }
-    std::vector<int32_t> counts;
-    if (heldout) {
-      hipLaunchKernelGGL(k_train_heldout, dim3(nb, P), dim3(kT), 0, c->stream, M, c->y.p, N, nb, c->m_counts.p);
-      HIPCHK(hipGetLastError());
-      counts.resize((size_t)P * (size_t)nb * 4);
-      COPY_SYNC(counts.data(), c->m_counts.p, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, c->stream);
-    }
-    std::vector<double> w((size_t)P * (size_t)VL);
-    HIPCHK(hipMemcpy2DAsync(w.data(), sizeof(double) * (size_t)VL, M.vec, sizeof(double) * (size_t)M.vec_stride,
-                            sizeof(double) * (size_t)VL, (size_t)P, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int q = 0; q < P; ++q) {
-      const double* wq = w.data() + (size_t)q * (size_t)VL;
-      for (int j = 0; j < c->D; ++j) out_W[(size_t)q * (size_t)c->D + (size_t)j] = wq[j] / 255.0;
-      out_rho[q] = -wq[c->Dp];
-      if (R[q].ls_fail && !R[q].converged) g_err = "the line search found no step (problem " + std::to_string(q) + ")";
-      if (stats) {
-        stats[q].objective = R[q].f;
-        stats[q].grad_norm = R[q].gnorm;
-        stats[q].grad_norm0 = R[q].gnorm0;
-        stats[q].outer_iters = outer[(size_t)q];
-        stats[q].cg_iters = R[q].cg_iters;
-        stats[q].converged = R[q].converged;
-        stats[q].n_active = R[q].n_active;
-      }
-      if (heldout) {
-        int32_t s[4] = {0, 0, 0, 0};
-        for (int b = 0; b < nb; ++b)  // in block order
-          for (int k = 0; k < 4; ++k) s[k] += counts[((size_t)q * (size_t)nb + (size_t)b) * 4 + (size_t)k];
-        heldout[q] = lm_train_heldout{s[0], s[1], s[2], s[3]};
-      }
-    }
+    const lm_train_problem one{c_pos, c_neg, -1, 0};
+    solve_problems(ctx, &one, 1, eps, max_iter, false, out_W, out_rho, stats, nullptr);
   });
 }
 
+// One X~ v pass as a one-problem call: the model in problem 0's hp (scratch outside a solve), the margins in its z.
 LM_API lm_status lm_train_margins(lm_train_ctx* ctx, const double* W, double rho, double* out_z) {
   if (!ctx || !W || !out_z) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
   if (ctx->n < 1) return fail(LM_ERR_INVALID_ARGUMENT, "the context holds no samples");
   return guarded([&] {
     lm_train_ctx* c = ctx;
     HIPCHK(hipSetDevice(c->device));
-    size_solver(c);
-    for (int j = 0; j < c->VL; ++j) c->h_vec.p[j] = j < c->D ? W[j] : 0.0;
-    c->h_vec.p[c->Dp] = -rho;
-    double* hp = c->vec.p + 5 * (size_t)c->VL;  // (scratch outside a solve)
-    COPY_SYNC(hp, c->h_vec.p, sizeof(double) * (size_t)c->VL, hipMemcpyHostToDevice, c->stream);
-    launch_xv(c, hp, 1.0, nullptr, c->smp.p, nullptr, GATE_NONE);
+    const LmtProblems M = bind_problems(c, 1);
+    std::vector<double> v((size_t)c->VL, 0.0);
+    for (int j = 0; j < c->D; ++j) v[(size_t)j] = W[j];
+    v[(size_t)c->Dp] = -rho;
+    COPY_SYNC(M.vec + (size_t)V_HP * (size_t)c->VL, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, c->stream);
+    launch_xv(c, M, V_HP, 1.0, S_NONE, S_Z, S_NONE, GATE_NONE);
     HIPCHK(hipGetLastError());
-    COPY_SYNC(out_z, c->smp.p, sizeof(double) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
+    COPY_SYNC(out_z, M.smp + (size_t)S_Z * (size_t)c->n, sizeof(double) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream);
   });
 }
 

@@ -51,11 +51,11 @@ LMT_HD double lmt_problem_cost(int y, int group, double c_pos, double c_neg, int
   return group == held_out ? 0.0 : (y > 0 ? c_pos : c_neg);
 }
 
-// Problems that share one pass over the matrix (lm_train.hip's _many kernels)
-// at D = kh * kw: their vectors, lmt_pitch(D) + 1 doubles each, fit into
-// LMT_MANY_LDS bytes of LDS, so that three workgroups share a CU's 160 KiB; at
-// most LMT_MANY_PB, which the 16 column sums per problem of k_train_xt_many
-// allow in registers.
+// Problems that share one pass over the matrix (lm_train.hip's k_train_xv and
+// k_train_xt) at D = kh * kw: their vectors, lmt_pitch(D) + 1 doubles each, fit
+// into LMT_MANY_LDS bytes of LDS, so that three workgroups share a CU's
+// 160 KiB; at most LMT_MANY_PB, which the 16 column sums per problem of
+// k_train_xt allow in registers.
 #define LMT_MANY_PB 4
 #define LMT_MANY_LDS (48 * 1024)
 LMT_HD int lmt_problem_block(int D) {
@@ -63,6 +63,32 @@ LMT_HD int lmt_problem_block(int D) {
   int pb = LMT_MANY_PB;
   while (pb > 1 && pb * bytes > LMT_MANY_LDS) pb >>= 1;
   return pb;
+}
+
+// The solver's arrays of one problem (lm_train.hip) for N samples and vectors
+// of VL doubles, in elements: the size of each, which is also the distance
+// between consecutive problems' arrays in a call's allocation.
+#define LMT_SAMPLE_BLOCK 256  // samples per workgroup of the per-sample kernels
+#define LMT_N_VEC 6           // vectors: w, g, d, r, p, hp
+#define LMT_N_SMP 5           // sample arrays: z, u, a, t, au
+struct LmtLayout {
+  int64_t nb, nblk;  // blocks of LMT_SAMPLE_BLOCK and of LMT_XT_BLOCK samples
+  int64_t vec;       // LMT_N_VEC x VL
+  int64_t smp;       // LMT_N_SMP x N
+  int64_t part;      // part_loss, part_act (nb each), then lspart (nb x LMT_LS_STEPS)
+  int64_t xtp;       // the X^T pass' block sums, nblk x VL
+  int64_t counts;    // the held-out counts, nb x 4 (int32)
+};
+LMT_HD LmtLayout lmt_layout(int64_t N, int VL) {
+  LmtLayout L;
+  L.nb = (N + LMT_SAMPLE_BLOCK - 1) / LMT_SAMPLE_BLOCK;
+  L.nblk = (N + LMT_XT_BLOCK - 1) / LMT_XT_BLOCK;
+  L.vec = (int64_t)LMT_N_VEC * VL;
+  L.smp = (int64_t)LMT_N_SMP * N;
+  L.part = L.nb * (2 + LMT_LS_STEPS);
+  L.xtp = L.nblk * VL;
+  L.counts = L.nb * 4;
+  return L;
 }
 
 // The change of sample i's loss when its margin goes from z to z + lambda xd.

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Rate of the batched SVM solver (lm_train_solve_many) against the single
-one (lm_train_solve) on one GPU.
+"""Rate of the SVM solver with many problems in one call (lm_train_solve_many)
+against the same problems as one-problem calls in turn (lm_train_solve, which
+is that: there is one solver) on one GPU: the comparison that justifies
+batching.
 
 The sample sets are those of scripts/train_rate.py, gathered the same way: the
 65,536 x 576 (24 x 24) and 65,536 x 900 (30 x 30) sets from 256 synthetic
@@ -10,8 +12,8 @@ held-out group, with the costs (10, 1) times scales spread geometrically over
 0.01 .. 100 (one problem: scale 1):
 
   many_ms   the wall time of one lm_train_solve_many call;
-  single_ms the sum of the wall times of lm_train_solve over the same
-            problems one after the other, in the same process;
+  single_ms the same problems as one-problem calls in turn: the sum of the
+            wall times of lm_train_solve over them, in the same process;
 
 each the best of --steps after --warmup.  The two return the same bits, which
 is checked here.  Then a real cross-validation call: 5 folds by frame x the 8
@@ -108,7 +110,7 @@ def main():
         line["sets"].append(measure_set(args, kh, kw, int(frames), int(samples)))
     line["value"] = line["sets"][0]["calls"][-1]["many_ms"]
     if not all(c["bit_identical"] for s in line["sets"] for c in s["calls"]):
-        raise SystemExit("the batched and the single solver differ: " + json.dumps(line))
+        raise SystemExit("a call of many problems and its problems in turn differ: " + json.dumps(line))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(line, fh, indent=1)
