@@ -364,6 +364,19 @@ lm_status lm_debug_tail_work(lm_ctx* ctx, int32_t* out);
  * context since its creation (it waits for the submitted batches to finish). */
 lm_status lm_debug_screen_fallback(lm_ctx* ctx, int64_t* out);
 
+/* The narrow class of ring work items (LM_CORR_NARROW=0 in the environment at
+ * lm_ctx_create: off).  A listed tile whose unproven 8-column blocks span at
+ * most two is computed as a 20 x 4 item, every other as the whole 40 x 4 tile.
+ * For detector ids 0 .. 5 in turn, out[2 d] = narrow and out[2 d + 1] = wide
+ * tiles of the last collected batch (their sum is the detector's listed
+ * count); -1 where the class is off or the detector's tile skip is. */
+lm_status lm_debug_narrow_work(lm_ctx* ctx, int32_t* out);
+/* The entries behind those counts: detector det's narrow (narrow != 0) or
+ * wide entries of the last collected batch, at most cap of them, *n written.
+ * An entry is slot << 16 | tile in its low word; a narrow one has its first
+ * unproven block | block count << 4 in the high word. */
+lm_status lm_debug_narrow_entries(lm_ctx* ctx, int32_t det, int32_t narrow, uint64_t* out, int32_t cap, int32_t* n);
+
 /* The flag bytes behind those counts for frame f of the last collected batch:
  * out[ty * cols + tx] = 1 when tile (ty, tx) of tail detector `view`
  * (0 bottom, 1 side) was listed; rows x cols = ceil(oh / tile height) x

@@ -18,6 +18,15 @@ LM_DEPTH_8U, LM_DEPTH_32F, LM_DEPTH_64F = 0, 5, 6
 DETECTORS = ("paw_bottom", "snout_bottom", "tail_bottom", "paw_side", "snout_side", "tail_side")
 
 
+def narrow_entry_fields(entries):
+    """(slot, tile, first block, block count) columns of the u64 entries of
+    lm_debug_narrow_entries (csrc/lm_corr_narrow.h: slot << 16 | tile in the
+    low word, first | count << 4 in the high word; 0, 0 for a wide entry)."""
+    e = np.asarray(entries, dtype=np.uint64)
+    lo, hi = (e & np.uint64(0xFFFFFFFF)).astype(np.int64), (e >> np.uint64(32)).astype(np.int64)
+    return np.stack([lo >> 16, lo & 0xFFFF, hi & 15, (hi >> 4) & 15], axis=1).reshape(-1, 4)
+
+
 class lm_rect(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "lm_corr_dir.h"
+#include "lm_corr_narrow.h"
 #include "lm_device.h"
 
 #define LM_CORR_THREADS 192
@@ -77,20 +78,39 @@ static_assert(LM_RW_HSLOTS >= (LM_FH == 4 ? 3 : 7), "k_corr_rw ring: rows live d
 // (the loads start on a 4-byte boundary), rounded to float4 stores (a lane
 // group's reads all hit one row of each sub-tile: the stride does not enter
 // the bank mapping)
-__host__ __device__ constexpr int rw_stride(int kw) { return (LM_FW + kw - 1 + 3 + 3) / 4 * 4; }
+// (fw: the work item's columns -- LM_FW, or LM_NW_FW for the narrow class of lm_corr_narrow.h)
+__host__ __device__ constexpr int rw_stride(int kw, int fw = LM_FW) { return (fw + kw - 1 + 3 + 3) / 4 * 4; }
 // floats per sub-tile ring: == LM_FW / 5 (mod 32).  A ds_read_b32 lane
 // group (32 lanes) holds one row group of 32 / (LM_FW / 5) sub-tiles; a
 // sub-tile's LM_FW / 5 lanes of a row group read columns 5 lx (mod 32) of one
 // ring row, and rings that start LM_FW / 5 floats apart (mod 32) put the
 // group's 32 reads on 32 banks (rw_tile).
-__host__ __device__ constexpr int rw_qpitch(int kw) {
-  return (LM_RW_HSLOTS + 1) * rw_stride(kw) +
-         ((LM_FW / 5 - ((LM_RW_HSLOTS + 1) * rw_stride(kw)) % 32) + 32) % 32;
+// Narrow items (4 lanes each, 8 of them in a lane group): rings that start
+// 4 m floats apart with m odd do the same -- item q's lane lx reads bank
+// 4 m q + 5 lx, and 4 m (q - q') == 5 (lx' - lx) (mod 32) needs 4 | lx' - lx,
+// so lx' == lx and then q' == q -- and the rings' rows are multiples of 4
+// floats, so the pitch is the rows rounded up to == 4 (mod 8): at most 4
+// floats of padding where == 4 (mod 32) took up to 28 (kw 30: 212 floats, the
+// 13.25 KB per wave that let three workgroups share a compute unit's LDS).
+__host__ __device__ constexpr int rw_qpitch(int kw, int fw = LM_FW) {
+  return fw == LM_FW ? (LM_RW_HSLOTS + 1) * rw_stride(kw) +
+                           ((LM_FW / 5 - ((LM_RW_HSLOTS + 1) * rw_stride(kw)) % 32) + 32) % 32
+                     : (LM_RW_HSLOTS + 1) * rw_stride(kw, fw) + ((4 - ((LM_RW_HSLOTS + 1) * rw_stride(kw, fw)) % 8) + 8) % 8;
 }
-__host__ __device__ constexpr int rw_ring_floats(int kw) { return LM_RW_NQ * rw_qpitch(kw); }
+__host__ __device__ constexpr int rw_nq(int fw = LM_FW) { return fw == LM_FW ? LM_RW_NQ : 64 / (fw / 5); }
+__host__ __device__ constexpr int rw_ring_floats(int kw, int fw = LM_FW) { return rw_nq(fw) * rw_qpitch(kw, fw); }
+// widths with narrow ring kernels (k_corr_rwn, k_corr_rwn_all): the ring
+// widths whose 16 window rows a wave loads with four dwords per lane
+#if defined(LM_KW_ONLY) || defined(LM_KW_C3)
+#define LM_KW_LIST_N LM_KW_LIST
+#else
+#define LM_KW_LIST_N(X) \
+  X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32) X(36) X(40)
+#endif
 // LDS of one ring workgroup at width kw (defined in lm_corr.hip, so it
 // follows the LM_RW_WAVES that the ring kernels were built with)
 size_t corr_rw_lds(int kw);
+size_t corr_rwn_lds(int kw);  // the same of a narrow ring workgroup
 
 // k_corr_f16 (non-parity LM_CORR_F16 mode): 2 x 2 waves per workgroup, each
 // with two 32 x 32 accumulator tiles side by side -> a 128 x 64 output tile
@@ -123,6 +143,9 @@ bool corr_ring(int kw);
 const void* corr_kernel(int kw, bool unf);     // k_corr_rw<kw> or k_corr_gen
 const void* corr_kernel_gen(bool unf);         // k_corr_gen (any size)
 const void* corr_kernel_rw_all(bool unf);      // every ring width in one launch
+bool corr_narrow_width(int kw);                // a width of LM_KW_LIST_N
+const void* corr_kernel_n(int kw, bool unf);   // k_corr_rwn<kw>, nullptr without one
+const void* corr_kernel_n_all(bool unf);       // the narrow items of every width of the merged launch
 const void* corr_kernel_f16(int kw);           // nullptr when kw is too wide
 // Dark tiles of a batch (written by k_ingest, lm_kernels.hip): flag bytes
 // per (slot, view, tile), the bright tiles' list per view and their counts.
@@ -145,6 +168,19 @@ struct CorrDark {
   int32_t* pt_cnt = nullptr;
   uint32_t* pt_list = nullptr;
 };
+// The narrow items of a detector group (lm_corr_narrow.h): nw_cnt: the lane's
+// LM_NW_CNT_WORDS counters, nw_list: the narrow entries (LmNarrowOut::n_list),
+// dir: the group's narrow record or null (the waves walk the group's
+// detectors).  The grid is lm_nw_grid_waves of the group.
+hipError_t launch_corr_n(const void* fn, int nslots, size_t lds, hipStream_t st, const LmConst* K, const LmDetGroup& G,
+                         const uint8_t* ext, int64_t ext_slot_bytes, const void* weights, unsigned long long* keys,
+                         int32_t* n_pos, uint8_t* tailbin, int64_t tailbin_slot_bytes, const int32_t* nw_cnt,
+                         const unsigned long long* nw_list, const LmCorrDirRecN* dir);
+// The narrow launches' directory: record b of `out` for narrow group b
+// (k_corr_dirn, once per batch next to k_corr_dir; sets LM_DEVERR_CORR_DIR
+// like it).
+hipError_t launch_corr_dir_n(hipStream_t st, const LmDetGroup* groups, int ngroups, int nslots, const int32_t* nw_cnt,
+                             LmCorrDirRecN* out, int32_t* err);
 // Launch the correlation for one detector group (`weights`: the fp32 rows, or
 // the f16 B fragments for k_corr_f16).  Ring kernels take one wave per tile
 // with the batch's tiles flattened (grid.y = slot count; with dark-tile lists

@@ -15,6 +15,9 @@
 //                       width of LM_KW_LIST, any height): one wave per 80 x 16
 //                       output tile streaming its window through a private
 //                       LDS ring; the production path.
+//   k_corr_rwn<KW, UNF> the same for the narrow class of work items (20 x 4
+//                       outputs on 4 lanes, 16 per wave: lm_corr_narrow.h), and
+//                       k_corr_rw_all / k_corr_rwn_all: every width in one launch.
 //   k_corr_dir          once per batch: the waves of each ring launch's
 //                       detectors (lm_corr_dir.h), so a ring wave finds its
 //                       work, or that it has none, from one scalar load.
@@ -238,6 +241,26 @@ struct RwRun {
       y = oy + (i / LM_RW_NQX) * LM_FH;
       x = ox + (i % LM_RW_NQX) * LM_FW;
     }
+  }
+};
+// A narrow wave's work (lm_corr_narrow.h): LM_NW_NQ narrow items from a
+// segment of a detector's narrow list.
+struct RwRunN {
+  const unsigned long long* l;  // the wave's first entry
+  int nvalid;
+  int ftx;
+  DEV unsigned long long entry(int i) const { return l[min(i, nvalid - 1)]; }
+  DEV void tile(int, unsigned long long e, int& s, int& y, int& x) const {
+    const uint32_t t = lm_nw_entry_tile(e);
+    const int lt = (int)(t & 0xFFFFu);
+    s = (int)(t >> 16);
+    y = (lt / ftx) * LM_FH;
+    x = (lt % ftx) * LM_FW + lm_nw_origin(lm_nw_entry_first(e));
+  }
+  // the output columns [x0, x1) the item owns
+  DEV void owned(unsigned long long e, int ow, int& x0, int& x1) const {
+    const int lt = (int)(lm_nw_entry_tile(e) & 0xFFFFu);
+    lm_nw_owned((lt % ftx) * LM_FW, lm_nw_entry_first(e), lm_nw_entry_count(e), ow, &x0, &x1);
   }
 };
 
@@ -567,10 +590,10 @@ DEV void rw_pair_1(lm_f2 (&a)[PK_C], lm_f2 w, const lm_f2* px) {
 #undef LM_RW_S0
 #undef LM_RW_S1
 
-template <int KW, bool UNF>
+template <int KW, bool UNF, int FW = LM_FW>
 struct RwPipe {
   using P = RwPlan<KW>;
-  static constexpr int STR = rw_stride(KW);
+  static constexpr int STR = rw_stride(KW, FW);
   lm_f2 px[PK_C + KW - 1];
   lm_f2 acc[2][PK_C];
   lm_f2 wa[P::PMAX], wb[P::PMAX];  // weight pairs of the chunk being computed (rows t, t - 2)
@@ -679,14 +702,19 @@ struct RwArgs {
 // load issued two steps earlier.  A wave's LDS operations run in order, so
 // no barrier anywhere.  The sub-tiles' row loads: load k of a lane is dword
 // dk of sub-tile qk's window row (lane + 64 k = qk NL + dk).
-template <int KW, bool UNF>
-DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const RwRun& R, float* ring) {
-  constexpr int NQ = LM_RW_NQ;
-  constexpr int QX = LM_FW / PK_C;  // lanes across a sub-tile
-  static_assert(LM_FH == PK_R && QX * NQ == 64, "one row of 8 lanes per 40 x 4 sub-tile");
-  constexpr int STR = rw_stride(KW);
-  constexpr int QP = rw_qpitch(KW);
-  constexpr int NL = (3 + LM_FW + KW - 1 + 3) / 4;  // dwords of a sub-tile's window row
+// FW, RUN: the work items' columns and where they come from -- LM_FW and RwRun,
+// or the narrow class (lm_corr_narrow.h): LM_NW_FW and RwRunN, 16 items of
+// 20 x 4 outputs on 4 lanes each, whose epilogue keeps only the outputs in the
+// columns the item owns.  The taps of an output and their order are the same.
+template <int KW, bool UNF, int FW = LM_FW, class RUN = RwRun>
+DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const RUN& R, float* ring) {
+  constexpr bool NARROW = FW != LM_FW;
+  constexpr int NQ = rw_nq(FW);
+  constexpr int QX = FW / PK_C;  // lanes across a sub-tile
+  static_assert(LM_FH == PK_R && QX * NQ == 64, "one row of FW / 5 lanes per FW x 4 work item (8 per 40 x 4 sub-tile, 4 per narrow item)");
+  constexpr int STR = rw_stride(KW, FW);
+  constexpr int QP = rw_qpitch(KW, FW);
+  constexpr int NL = (3 + FW + KW - 1 + 3) / 4;  // dwords of a sub-tile's window row
   constexpr int NLD = (NQ * NL + 63) / 64;          // dwords a lane loads per row
   static_assert(NLD <= 4, "window rows wider than four loads per lane");
   constexpr int HS = LM_RW_HSLOTS;
@@ -813,7 +841,7 @@ DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const 
   auto row_base = [&](int t) -> unsigned {  // the slot offset as one scalar: one vector add per row
     return ring_lane + (unsigned)__builtin_amdgcn_readfirstlane((t % HS) * STR * (int)sizeof(float));
   };
-  RwPipe<KW, UNF> S;
+  RwPipe<KW, UNF, FW> S;
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -861,17 +889,40 @@ DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const 
   // epilogue (the ring is dead: this wave's reads were issued first)
   unsigned bits = 0;
   if (valid) {
+    // a narrow item keeps the outputs of the columns it owns (its entry is read again here, not held in registers
+    // through the steps): the block next to them may be another item's, and a key must appear once
+    int own0 = 0, own1 = D.ow;
+    if constexpr (NARROW) R.owned(R.entry(q), D.ow, own0, own1);
 #pragma unroll
     for (int p = 0; p < PK_R / 2; ++p)
 #pragma unroll
       for (int c = 0; c < PK_C; ++c) {
         const int x = ox0 + lx * PK_C + c;
         const int y0 = oy0 + 2 * p;
-        if (x < D.ow && y0 < D.oh && S.acc[p][c].x > 0.0f) bits |= 1u << ((2 * p) * PK_C + c);
-        if (x < D.ow && y0 + 1 < D.oh && S.acc[p][c].y > 0.0f) bits |= 1u << ((2 * p + 1) * PK_C + c);
+        const bool in = NARROW ? x >= own0 && x < own1 : x < D.ow;
+        if (in && y0 < D.oh && S.acc[p][c].x > 0.0f) bits |= 1u << ((2 * p) * PK_C + c);
+        if (in && y0 + 1 < D.oh && S.acc[p][c].y > 0.0f) bits |= 1u << ((2 * p + 1) * PK_C + c);
       }
   }
-  if (D.kind != 0) {
+  if constexpr (NARROW) {
+    if (D.kind != 0) {
+      // tail map: an item's owned columns may straddle two bitmap words (a 16-column span at 24 mod 32), and very
+      // few items have a bit at all: one global atomicOr per set bit
+      unsigned* __restrict__ tb = reinterpret_cast<unsigned*>(A.tailbin + (int64_t)slot * A.tailbin_slot_bytes) +
+                                  (D.list ? (int64_t)K.tail_hb * K.tail_nw : 0);
+#pragma unroll
+      for (int r = 0; r < PK_R; ++r)
+#pragma unroll
+        for (int c = 0; c < PK_C; ++c)
+          if (bits & (1u << (r * PK_C + c))) {
+            const int x = ox0 + lx * PK_C + c, y = oy0 + r;
+            if ((x >> 5) < K.tail_nw) atomicOr(&tb[(int64_t)y * K.tail_nw + (x >> 5)], 1u << (x & 31));
+          }
+      return;
+    }
+  }
+  if constexpr (!NARROW) {
+   if (D.kind != 0) {
     // tail map, each sub-tile on its own (listed sub-tiles are any tiles of
     // any slots of a segment): its LM_FH rows x WPS u32 words (the origin is
     // a multiple of LM_FW, so its columns touch at most WPS words) = one
@@ -898,6 +949,7 @@ DEV __attribute__((always_inline)) void rw_tile(const RwArgs& A, int dix, const 
     const int y = oy0 + lx / WPS, gw = w0 + lx % WPS;
     if (v && y < D.oh && gw < K.tail_nw) atomicOr(&tb[(int64_t)y * K.tail_nw + gw], v);
     return;
+   }
   }
   bits &= mbits;
   // keys: each lane's set bits at consecutive places after the lanes of its
@@ -1009,6 +1061,132 @@ __global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(L
 #define LM_KW_CASE(n)           \
   case n:                       \
     rw_tile<n, UNF>(a, d, R, ring); \
+    break;
+    LM_KW_LIST_RW_ALL(LM_KW_CASE)
+#undef LM_KW_CASE
+    default:
+      break;
+  }
+}
+
+// ------------------------------------------------------- the narrow launches
+// The narrow items of the listed tiles (lm_corr_narrow.h; k_tile_bound wrote
+// them, with the wide lists the kernels above then read): launches of their
+// own, since a narrow wave's 16 rings are larger than a wide wave's 8 (kw 26:
+// 12.3 KB against 9.5 KB) and one launch sized for both takes the wide
+// waves from four to three per SIMD (measured: 208 us for the one launch
+// against 98 + 95 us, profiles/narrow/).  A narrow launch holds three waves per
+// SIMD up to kw 30.  Its work is flattened like a wide launch's: the narrow
+// waves of the group's first detector, then the next one's, ceil(cnt / 16)
+// waves per list segment; ncnt: the lane's counters (LM_NW_CNT_N: 64 per
+// detector id), nlist: the entries.
+DEV bool corr_locate_n(const LmConst& K, const LmDetGroup& G, int nslots, int g, const int32_t* __restrict__ ncnt,
+                       const unsigned long long* __restrict__ nlist, const LmCorrDirRecN* __restrict__ dir, int& d,
+                       RwRunN& R) {
+  const int lane = threadIdx.x & 63;
+  int k = 0, local = 0;
+  if (dir) {
+    typedef int32_t lm_i8 __attribute__((ext_vector_type(8)));
+    const lm_i8 rv = *reinterpret_cast<const lm_i8*>(dir);
+    const LmCorrDirRecN rec{{rv[0], rv[1], rv[2], rv[3], rv[4], rv[5]}, rv[6], rv[7]};
+    if (!lm_nw_lookup(rec, G.n, g, &k, &local)) return false;
+  } else {  // the walk (LM_CORR_DIR=0)
+    int base = 0;
+    bool found = false;
+#pragma unroll
+    for (int kk = 0; kk < LM_NDET; ++kk) {
+      if (kk >= G.n || found) continue;
+      const int wv = lm_nw_seg_waves(ncnt[LM_NW_CNT_N + G.ids[kk] * LM_TL_NC + lane]);
+      const int tot = __builtin_amdgcn_readlane(corr_scan_waves(wv), 63);
+      if (g < base + tot) {
+        k = kk;
+        local = g - base;
+        found = true;
+      }
+      base += tot;
+    }
+    if (!found) return false;
+  }
+  const int dk = G.ids[k];
+  const LmDet& D = K.det[dk];
+  const int cn = ncnt[LM_NW_CNT_N + dk * LM_TL_NC + lane];
+  const int wv = lm_nw_seg_waves(cn);
+  const int P = corr_scan_waves(wv);
+  const int c = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(P > local)) - 1);
+  const int w = local - (__builtin_amdgcn_readlane(P, c) - __builtin_amdgcn_readlane(wv, c));  // place in segment c
+  const bool pt = D.kind == 0;
+  const int v = pt ? D.view : D.list;
+  const int ftx = pt ? K.fl_tx[v] : K.tt_tx[v], ntile = ftx * (pt ? K.fl_ty[v] : K.tt_ty[v]);
+  const int ng = (nslots + LM_INGEST_FB - 1) / LM_INGEST_FB;
+  const unsigned long long* lst =
+      nlist + (pt ? (int64_t)D.list * K.tl_stride : (int64_t)LM_NLIST * K.tl_stride + (int64_t)v * K.tt_stride);
+  d = dk;
+  R = RwRunN{lst + (int64_t)lm_tl_y0(c, ng) * LM_INGEST_FB * ntile + LM_NW_NQ * w,
+             min(LM_NW_NQ, __builtin_amdgcn_readlane(cn, c) - LM_NW_NQ * w), ftx};
+  return true;
+}
+
+struct LmCorrDirGroupsN {
+  int32_t n;
+  int32_t grid[LM_NDET];  // waves of group b's launch
+  LmDetGroup g[LM_NDET];
+};
+__global__ __launch_bounds__(64) void k_corr_dirn(const LmCorrDirGroupsN A, const int32_t* __restrict__ ncnt,
+                                                   LmCorrDirRecN* __restrict__ out, int32_t* __restrict__ err) {
+  const int b = blockIdx.x;
+  const LmDetGroup& G = A.g[b];
+  const int lane = threadIdx.x;
+  int32_t waves[LM_NDET];
+#pragma unroll
+  for (int k = 0; k < LM_NDET; ++k) {
+    waves[k] = 0;
+    if (k < G.n)
+      waves[k] = __builtin_amdgcn_readlane(corr_scan_waves(lm_nw_seg_waves(ncnt[LM_NW_CNT_N + G.ids[k] * LM_TL_NC + lane])), 63);
+  }
+  if (lane == 0) {
+    const LmCorrDirRecN rec = lm_nw_record(waves, G.n);
+    out[b] = rec;
+    if (rec.total > A.grid[b]) atomicOr(err, LM_DEVERR_CORR_DIR);
+  }
+}
+
+#define LM_RWN_WPE 3  // waves per SIMD of the narrow launches: what their rings allow up to kw 30
+template <int KW, bool UNF>
+__global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(KW <= 32 ? LM_RWN_WPE : 1, 8))) void k_corr_rwn(
+    const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
+    const float* __restrict__ weights, int nslots, unsigned long long* __restrict__ keys, int32_t* __restrict__ n_pos,
+    uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes, const int32_t* __restrict__ ncnt,
+    const unsigned long long* __restrict__ nlist, const LmCorrDirRecN* __restrict__ dir) {
+  extern __shared__ uint4 lds_rw[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float* ring = reinterpret_cast<float*>(lds_rw) + wave * rw_ring_floats(KW, LM_NW_FW);
+  const RwArgs a{Kp, G, ext, ext_slot_bytes, weights, 0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
+                 nullptr, nullptr, 0, nullptr, nullptr};
+  int d;
+  RwRunN R;
+  if (!corr_locate_n(*a.K, G, nslots, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, ncnt, nlist, dir, d, R)) return;
+  rw_tile<KW, UNF, LM_NW_FW, RwRunN>(a, d, R, ring);
+}
+
+// The narrow items of every detector of the merged launch (G.ring_floats: the widest detector's narrow rings).
+template <bool UNF>
+__global__ __launch_bounds__(LM_RW_THREADS) __attribute__((amdgpu_waves_per_eu(LM_RWN_WPE, 8))) void k_corr_rwn_all(
+    const LmConst* __restrict__ Kp, const LmDetGroup G, const uint8_t* __restrict__ ext, int64_t ext_slot_bytes,
+    const float* __restrict__ weights, int nslots, unsigned long long* __restrict__ keys, int32_t* __restrict__ n_pos,
+    uint8_t* __restrict__ tailbin, int64_t tailbin_slot_bytes, const int32_t* __restrict__ ncnt,
+    const unsigned long long* __restrict__ nlist, const LmCorrDirRecN* __restrict__ dir) {
+  extern __shared__ uint4 lds_rw[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  float* ring = reinterpret_cast<float*>(lds_rw) + wave * G.ring_floats;
+  const RwArgs a{Kp, G, ext, ext_slot_bytes, weights, 0, nslots, keys, n_pos, tailbin, tailbin_slot_bytes,
+                 nullptr, nullptr, 0, nullptr, nullptr};
+  int d;
+  RwRunN R;
+  if (!corr_locate_n(*a.K, G, nslots, xcd_block(blockIdx.x, gridDim.x) * LM_RW_WAVES + wave, ncnt, nlist, dir, d, R)) return;
+  switch (a.K->det[d].kw_ring) {
+#define LM_KW_CASE(n)                                   \
+  case n:                                               \
+    rw_tile<n, UNF, LM_NW_FW, RwRunN>(a, d, R, ring); \
     break;
     LM_KW_LIST_RW_ALL(LM_KW_CASE)
 #undef LM_KW_CASE
@@ -1399,6 +1577,58 @@ const void* corr_kernel(int kw, bool unf) {
 }
 
 size_t corr_rw_lds(int kw) { return (size_t)LM_RW_WAVES * rw_ring_floats(kw) * sizeof(float); }
+size_t corr_rwn_lds(int kw) { return (size_t)LM_RW_WAVES * rw_ring_floats(kw, LM_NW_FW) * sizeof(float); }
+
+bool corr_narrow_width(int kw) {
+  switch (kw) {
+#define LM_KW_CASE(n) case n:
+    LM_KW_LIST_N(LM_KW_CASE)
+#undef LM_KW_CASE
+    return true;
+    default:
+      return false;
+  }
+}
+
+const void* corr_kernel_n(int kw, bool unf) {
+  switch (kw) {
+#define LM_KW_CASE(n) \
+  case n:             \
+    return unf ? (const void*)&k_corr_rwn<n, true> : (const void*)&k_corr_rwn<n, false>;
+    LM_KW_LIST_N(LM_KW_CASE)
+#undef LM_KW_CASE
+    default:
+      return nullptr;
+  }
+}
+
+const void* corr_kernel_n_all(bool unf) {
+  return unf ? (const void*)&k_corr_rwn_all<true> : (const void*)&k_corr_rwn_all<false>;
+}
+
+hipError_t launch_corr_n(const void* fn, int nslots, size_t lds, hipStream_t st, const LmConst* K, const LmDetGroup& G,
+                         const uint8_t* ext, int64_t ext_slot_bytes, const void* weights, unsigned long long* keys,
+                         int32_t* n_pos, uint8_t* tailbin, int64_t tailbin_slot_bytes, const int32_t* nw_cnt,
+                         const unsigned long long* nw_list, const LmCorrDirRecN* dir) {
+  const unsigned waves = (unsigned)lm_nw_grid_waves(G.tile_end[G.n - 1], nslots, G.n);
+  void* args[] = {(void*)&K,    (void*)&G,     (void*)&ext,     (void*)&ext_slot_bytes,     (void*)&weights,
+                  (void*)&nslots, (void*)&keys, (void*)&n_pos,   (void*)&tailbin, (void*)&tailbin_slot_bytes,
+                  (void*)&nw_cnt, (void*)&nw_list, (void*)&dir};
+  return hipLaunchKernel(fn, dim3((waves + LM_RW_WAVES - 1) / LM_RW_WAVES), dim3(LM_RW_THREADS), args, lds, st);
+}
+
+hipError_t launch_corr_dir_n(hipStream_t st, const LmDetGroup* groups, int ngroups, int nslots, const int32_t* nw_cnt,
+                             LmCorrDirRecN* out, int32_t* err) {
+  if (ngroups < 1 || ngroups > LM_NDET) return hipErrorInvalidValue;
+  LmCorrDirGroupsN A{};
+  A.n = ngroups;
+  for (int b = 0; b < ngroups; ++b) {
+    A.g[b] = groups[b];
+    A.grid[b] = lm_nw_grid_waves(groups[b].tile_end[groups[b].n - 1], nslots, groups[b].n);
+  }
+  k_corr_dirn<<<ngroups, 64, 0, st>>>(A, nw_cnt, out, err);
+  return hipGetLastError();
+}
 
 const void* corr_kernel_gen(bool unf) { return unf ? (const void*)&k_corr_gen<true> : (const void*)&k_corr_gen<false>; }
 

@@ -167,6 +167,10 @@ struct LmConst {
   // tbs_bf[d], tbs_e[d]: its bias rounded up and its margin
   int32_t tbs_on[LM_NDET], tbs_off[LM_NDET];
   float tbs_bf[LM_NDET], tbs_e[LM_NDET];
+  // the narrow class of ring work items (lm_corr_narrow.h): nw_on[d]: k_tile_bound
+  // splits detector d's kept tiles into narrow and wide ones (LM_CORR_NARROW,
+  // tbr_on[d], a ring width with a narrow kernel); 0: all of them are wide
+  int32_t nw_on[LM_NDET];
   // the point detectors' output region per view: output (y, x) has its
   // I_*_MOUSE pixel at ext (fl_my + y, fl_mx + x); fl_oh x fl_ow outputs
   int32_t fl_my[2], fl_mx[2], fl_oh[2], fl_ow[2];

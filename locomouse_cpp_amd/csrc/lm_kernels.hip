@@ -34,6 +34,7 @@
 #include "lm_introsort.h"
 
 #include "lm_dev_common.h"
+#include "lm_corr_narrow.h"
 #include "lm_tail_bound.h"
 #include "lm_tile_plan.h"
 
@@ -888,15 +889,29 @@ DEV int wave_append(bool p, int* ctr) {
 // TBW_SEL: detector k's member of one of the kernel's per-detector arrays,
 // chosen among the three uniform values, not loaded per lane.
 #define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
-template <bool ROWS>
+// NARROW (LM_CORR_NARROW, lm_corr_narrow.h): step 4b marks an entry with the
+// mask of its unproven blocks instead of 0 / 1, the masks close up with the
+// entries, and step 5 also appends every kept entry to one of two further
+// lists of its detector, which the ring kernels then read in place of the
+// existing ones: narrow (the unproven blocks span at most two: the entry with
+// the span's first block and length) or wide (every other, as in the existing
+// list; all of a detector that is not refined or has LmConst::nw_on 0).  The
+// existing flags, lists and counters are written as without it.
+template <bool ROWS, bool NARROW>
 __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(LM_TBW_WPE, 8))) void k_tile_bound(
     const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
     const double* __restrict__ tbc, const uint8_t* __restrict__ bright, uint8_t* __restrict__ tail_flags,
     int32_t* __restrict__ tt_cnt, uint32_t* __restrict__ tt_list, uint8_t* __restrict__ pt_flags,
-    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list, unsigned long long* __restrict__ tbs_fallback) {
+    int32_t* __restrict__ pt_cnt, uint32_t* __restrict__ pt_list, unsigned long long* __restrict__ tbs_fallback,
+    const LmNarrowOut nwo) {
   const LmConst& K = *Kp;
   extern __shared__ __attribute__((aligned(16))) uint8_t tbw_lds[];
   __shared__ int s_n[3], s_b[3], s_m[3], s_base[3], s_nw;
+  __shared__ int s_c[3][2], s_g[3][2], s_p[3][2];  // NARROW: entries, list places and entries written per (detector, class)
+  if (NARROW && threadIdx.x < 6) {
+    s_c[threadIdx.x >> 1][threadIdx.x & 1] = 0;
+    s_p[threadIdx.x >> 1][threadIdx.x & 1] = 0;
+  }
   const int v = (int)blockIdx.y < K.tbw_nband[0] ? 0 : 1;
   const int band = (int)blockIdx.y - (v ? K.tbw_nband[0] : 0);
   const int slot = s0 + (int)blockIdx.x;
@@ -1289,7 +1304,11 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
           for (int r = 0; r < nr && proven; ++r) proven = level_b(r, 1);
         }
       }
-      if (!proven) mark[mb + t] = 1u;
+      if constexpr (NARROW) {  // (a short last tile row is not tried per 4-row block: its tiles stay wide)
+        if (!proven) atomicOr(&mark[mb + t], 1u << (e - t * LM_TB_NBX) | (nr != LM_TB_H ? LM_NW_UNTRIED : 0u));
+      } else {
+        if (!proven) mark[mb + t] = 1u;
+      }
     }
     __syncthreads();
     // the marked entries of each detector close up: a group of entries is read
@@ -1298,7 +1317,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     // group of LM_TBW_CR * T entries, which a band's entries rarely exceed)
     constexpr int CR = LM_TBW_CR;
     for (int g0 = 0; g0 < nref; g0 += CR * T) {
-      uint32_t en[CR];
+      uint32_t en[CR], mk[CR];
       int kk[CR];
 #pragma unroll
       for (int u = 0; u < CR; ++u) {
@@ -1307,7 +1326,9 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
         const int k = i < nr3[0] ? 0 : i < nr3[0] + nr3[1] ? 1 : 2;
         const int t = i - (k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]);
         en[u] = act ? reinterpret_cast<const uint32_t*>(tbw_lds + TBW_SEL(ent3))[t] : 0u;
-        const bool kp = act && mark[i] != 0u;
+        mk[u] = act ? mark[i] : 0u;
+        const bool kp = mk[u] != 0u;
+
         kk[u] = kp ? k : -1;
         if (act) TBW_SEL(fl)[en[u] & 0xFFFFu] = kp ? 1 : 0;
       }
@@ -1319,6 +1340,8 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
           const bool mine = kk[u] == k;
           const int pos = wave_append(mine, &s_m[k]);
           if (mine) reinterpret_cast<uint32_t*>(tbw_lds + ent3[k])[pos] = en[u];
+          // (the entry's mask moves with it: down or not at all inside its detector's marks, like the entry)
+          if (NARROW && mine) mark[(k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]) + pos] = mk[u];
         }
     }
     __syncthreads();
@@ -1348,6 +1371,64 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
         (tail[k] ? tt_list + (int64_t)v * K.tt_stride : pt_list + (int64_t)D.list * K.tl_stride) +
         (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
     for (int p = tid; p < s_n[k]; p += T) out[p] = ent[p];
+  }
+  // 5n. the same entries once more, by class (NARROW): counted, one global
+  // atomic per (workgroup, detector, class) on the class's segment counter,
+  // then written
+  if constexpr (NARROW) {
+    if (nwo.cnt == nullptr) return;
+    bool split[3];
+    int mbk[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      split[k] = refine[k] && K.nw_on[3 * v + k] != 0;
+      mbk[k] = k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!on[k]) continue;
+      const int n = s_n[k];
+      for (int p0 = 0; p0 < n; p0 += T) {
+        const int p = p0 + tid;
+        const bool act = p < n, nar = act && split[k] && lm_nw_classify(mark[mbk[k] + p]).narrow != 0;
+        const unsigned long long mn = __ballot(nar), mw = __ballot(act && !nar);
+        if ((tid & 63) == 0) {
+          if (mn != 0ull) atomicAdd(&s_c[k][1], (int)__popcll(mn));
+          if (mw != 0ull) atomicAdd(&s_c[k][0], (int)__popcll(mw));
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < 6 && on[tid >> 1]) {
+      const int k = tid >> 1, cls = tid & 1, d = 3 * v + k;
+      const LmDet& D = K.det[d];
+      int32_t* __restrict__ cnt = nwo.cnt + (cls ? LM_NW_CNT_N + d * LM_TL_NC
+                                                 : D.kind != 0 ? LM_NW_CNT_TTW + v * LM_TL_NC : LM_NW_CNT_PTW + D.list * LM_TL_NC);
+      s_g[k][cls] = s_c[k][cls] ? atomicAdd(&cnt[c], s_c[k][cls]) : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!on[k]) continue;
+      const int n = s_n[k];
+      const LmDet& D = K.det[3 * v + k];
+      const int ntile = tail[k] ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
+      const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + K.tbw_ent[3 * v + k]);
+      const int64_t lo = tail[k] ? (int64_t)v * K.tt_stride : (int64_t)D.list * K.tl_stride;  // the detector's lists
+      const int64_t so = (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile;                      // the segment in them
+      uint32_t* __restrict__ wout = (tail[k] ? nwo.ttw_list : nwo.ptw_list) + lo + so + s_g[k][0];
+      unsigned long long* __restrict__ nout = nwo.n_list + (tail[k] ? (int64_t)LM_NLIST * K.tl_stride : 0) + lo + so + s_g[k][1];
+      for (int p0 = 0; p0 < n; p0 += T) {
+        const int p = p0 + tid;
+        const bool act = p < n;
+        const LmNwClass cl = act && split[k] ? lm_nw_classify(mark[mbk[k] + p]) : LmNwClass{0, 0, 0};
+        const bool nar = cl.narrow != 0;
+        const int pn = wave_append(nar, &s_p[k][1]);
+        if (nar) nout[pn] = lm_nw_entry(ent[p], cl.first, cl.count);
+        const int pw = wave_append(act && !nar, &s_p[k][0]);
+        if (act && !nar) wout[pw] = ent[p];
+      }
+    }
   }
 }
 #undef TBW_SEL
@@ -3182,7 +3263,8 @@ __global__ __launch_bounds__(256) void k_prep(const LmSlot* __restrict__ h_slots
                                               const LmConst* __restrict__ Kp, unsigned long long* __restrict__ keys,
                                               const LmSlotOut* __restrict__ prev_hdr, int prev_slot,
                                               LmSlotOut* __restrict__ hdr, int32_t* __restrict__ dark_cnt,
-                                              int32_t* __restrict__ tail_cnt, int32_t* __restrict__ pt_cnt) {
+                                              int32_t* __restrict__ tail_cnt, int32_t* __restrict__ pt_cnt,
+                                              int32_t* __restrict__ nw_cnt) {
   if (blockIdx.x == 1) {
     carry_block(*Kp, keys, prev_hdr, prev_slot, hdr);
     return;
@@ -3192,6 +3274,10 @@ __global__ __launch_bounds__(256) void k_prep(const LmSlot* __restrict__ h_slots
   if (pt_cnt) {  // and its point-tile counters (listed and bright tiles per detector)
     pt_cnt[threadIdx.x] = 0;
     pt_cnt[256 + threadIdx.x] = 0;
+  }
+  if (nw_cnt) {  // and the counters of its narrow and wide lists (lm_corr_narrow.h)
+    static_assert(LM_NW_CNT_WORDS == 3 * 256, "k_prep zeroes the narrow / wide counters with its 256 threads");
+    for (int i = 0; i < 3; ++i) nw_cnt[256 * i + threadIdx.x] = 0;
   }
   for (int i = threadIdx.x; i < ns; i += blockDim.x) {
     slots[i] = h_slots[i];

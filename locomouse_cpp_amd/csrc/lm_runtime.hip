@@ -116,6 +116,12 @@ struct Lane {
   DevBuf<int32_t> pt_cnt;    // per list id 64 segment counters of listed tiles, then of bright tiles
   DevBuf<uint32_t> rng;      // k_ingest's block ranges for k_tile_bound: one word per 16-byte chunk of ext
   DevBuf<LmCorrDirRec> corr_dir;  // k_corr_dir's record per launch group of the batch's correlation plan
+  // the narrow class (lm_corr_narrow.h, lm_ctx::narrow_on): k_tile_bound's counters of the wide and narrow lists, the
+  // wide lists in the layout of pt_list / tail_list, the narrow entries, and k_corr_dirn's record per narrow group
+  DevBuf<int32_t> nw_cnt;
+  DevBuf<uint32_t> ptw_list, ttw_list;
+  DevBuf<unsigned long long> nw_list;
+  DevBuf<LmCorrDirRecN> corr_dirn;
   HostBuf<int32_t> h_cnt;   // debug bit 1: dark_cnt of the submitted batch, copied on its stream
   bool h_cnt_valid = false;
   DevBuf<long long> kprof;  // LM_KPROF=1: kernel phase timestamps
@@ -205,6 +211,9 @@ struct lm_ctx {
     std::vector<size_t> lds;                                 // dynamic LDS bytes per group launch
     std::vector<int> threads;                                // block size per group launch
     std::vector<char> ring;                                  // group runs k_corr_rw* (one wave per tile)
+    // the narrow launches (narrow_on): the ring detectors with LmConst::nw_on, grouped like the ring groups above
+    std::vector<std::pair<const void*, LmDetGroup>> ngroups;  // (k_corr_rwn<kw> or k_corr_rwn_all, its detectors)
+    std::vector<size_t> nlds;
   } corr_plan[2];
   // frame-invariant device data
   DevBuf<uint8_t> bkg, adj;
@@ -237,6 +246,11 @@ struct lm_ctx {
   // LM_CORR_DIR=0: no k_corr_dir; the ring correlation's waves walk their
   // group's detectors to find their work (lm_corr.hip corr_locate_walk)
   bool corr_dir_on = true;
+  // LM_CORR_NARROW=0: no narrow class of ring work items (lm_corr_narrow.h).  narrow_req: the switch as read;
+  // narrow_on: some detector has LmConst::nw_on (never with LM_TILE_REFINE=0, LM_TILE_BOUND_REF=1, the f16 mode, or
+  // for detectors whose tile skip is off): k_tile_bound<., true> writes the narrow and wide lists, the ring kernels
+  // read the wide lists and the narrow launches follow them
+  bool narrow_req = true, narrow_on = false;
   size_t tb_lds = 0;        // k_tile_bound_ref's LDS bytes (the larger view's)
   size_t tbw_lds = 0;       // k_tile_bound's (the larger view's band)
   // a detector that k_tile_bound refines has one chunk of group constants per
@@ -415,6 +429,7 @@ LmTileSwitches read_switches(lm_ctx* c, const lm_setup* su) {
   c->tb_screen = flag("LM_TILE_SCREEN", true);
   c->tb_ref = flag("LM_TILE_BOUND_REF", false);
   c->corr_dir_on = flag("LM_CORR_DIR", true);
+  c->narrow_req = flag("LM_CORR_NARROW", true);
   LmTileSwitches sw;
   sw.tailskip = flag("LM_CORR_TAILSKIP", true);
   sw.pointskip = flag("LM_CORR_POINTSKIP", true);
@@ -745,6 +760,52 @@ void slot_sizes(lm_ctx* c) {
 // windows need, so narrow groups keep more waves per CU.  Reads det[] and the
 // setup's precision and filter arithmetic; fills c->unfused, c->corr_plan[]
 // and det[].chunk_rows.
+// The narrow class: which detectors k_tile_bound splits (K.nw_on), and each
+// plan's narrow launches -- a ring group's detectors with nw_on, run by the
+// group's narrow kernel.  After lm_tile_plan (reads tbr_on, tbw_use) and
+// before the constants' upload.
+void build_narrow_plans(lm_ctx* c, const lm_setup* su) {
+  LmConst& K = c->K;
+  const bool f16 = su->corr_precision == LM_CORR_F16;
+  c->narrow_on = false;
+  for (int d = 0; d < LM_NDET; ++d) {
+    const LmDet& D = K.det[d];
+    const bool ring = !f16 && corr_ring(D.kw_ring) && D.kh >= 2;
+    K.nw_on[d] = c->narrow_req && !c->tb_ref && c->tb_refine && c->dark_on && ring && corr_narrow_width(D.kw_ring) &&
+                 K.tbr_on[d] != 0 && K.tbw_use[d] != 0 && (D.kind != 0 ? c->tailskip_on : c->pointskip_on);
+    c->narrow_on = c->narrow_on || K.nw_on[d] != 0;
+  }
+  for (int m = 0; m < 2; ++m) {
+    lm_ctx::CorrPlan& P = c->corr_plan[m];
+    P.ngroups.clear();
+    P.nlds.clear();
+    for (size_t gi = 0; gi < P.groups.size(); ++gi) {
+      if (!P.ring[gi]) continue;
+      const LmDetGroup& G = P.groups[gi].second;
+      const bool all = P.groups[gi].first == corr_kernel_rw_all(c->unfused);
+      LmDetGroup N;
+      std::memset(&N, 0, sizeof(N));
+      size_t lds = 0;
+      const void* fn = nullptr;
+      for (int k = 0; k < G.n; ++k) {
+        const int d = G.ids[k];
+        if (!K.nw_on[d]) continue;
+        const LmDet& D = K.det[d];
+        const int prev = N.n ? N.tile_end[N.n - 1] : 0;
+        N.ids[N.n] = d;
+        N.tile_end[N.n] = prev + D.tiles_x * D.tiles_y;
+        ++N.n;
+        N.ring_floats = std::max(N.ring_floats, rw_ring_floats(D.kw_ring, LM_NW_FW));
+        lds = std::max(lds, corr_rwn_lds(D.kw_ring));
+        fn = all ? corr_kernel_n_all(c->unfused) : corr_kernel_n(D.kw_ring, c->unfused);
+      }
+      if (N.n == 0) continue;
+      P.ngroups.push_back({fn, N});
+      P.nlds.push_back(lds);
+    }
+  }
+}
+
 void build_corr_plans(lm_ctx* c, const lm_setup* su) {
   LmConst& K = c->K;
   c->unfused = su->filter_arith == LM_FILTER_UNFUSED;
@@ -892,11 +953,18 @@ void upload_constants(lm_ctx* c, const lm_setup* su, const std::vector<float>& w
   c->fstride = (nv + 255) / 256 * 256;
   HIPCHK(hipFuncSetAttribute((const void*)k_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tail_lds));
   HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound_ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tb_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
-  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
-  for (const auto& P : c->corr_plan)
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+  HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+  if (c->narrow_on) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_tile_bound<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->tbw_lds));
+  }
+  for (const auto& P : c->corr_plan) {
     for (size_t g = 0; g < P.groups.size(); ++g)
       HIPCHK(hipFuncSetAttribute(P.groups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds[g]));
+    for (size_t g = 0; g < P.ngroups.size(); ++g)
+      HIPCHK(hipFuncSetAttribute(P.ngroups[g].first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.nlds[g]));
+  }
 }
 
 void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const lm_model* M) {
@@ -929,6 +997,7 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   c->tb_lds = plan.tb_lds;
   c->tbw_lds = plan.tbw_lds;
   c->tbw_row_loop = plan.row_loop;
+  build_narrow_plans(c, su);
   const std::vector<_Float16> w16 = f16_fragments(K, su, M);
   uint8_t adj[256];
   imadjust_table(adj);
@@ -989,6 +1058,16 @@ void lane_alloc(lm_ctx* c, Lane& L) {
   if ((c->tailskip_on || c->pointskip_on) && !c->tb_ref) {
     L.rng.alloc((size_t)(c->ext_slot_bytes / LM_INGEST_VEC) * ns);
     SET_SYNC(L.rng.p, 0, (size_t)(c->ext_slot_bytes / LM_INGEST_VEC) * ns * sizeof(uint32_t), st);
+  }
+  if (c->narrow_on) {
+    L.nw_cnt.alloc(LM_NW_CNT_WORDS);
+    SET_SYNC(L.nw_cnt.p, 0, LM_NW_CNT_WORDS * sizeof(int32_t), st);
+    // (a list of a skip that is off is never written or read; one word keeps its pointer valid)
+    L.ptw_list.alloc(c->pointskip_on ? (size_t)LM_NLIST * K.tl_stride : 1);
+    L.ttw_list.alloc(c->tailskip_on ? (size_t)2 * K.tt_stride : 1);
+    L.nw_list.alloc((size_t)LM_NLIST * K.tl_stride + (size_t)2 * K.tt_stride);
+    L.corr_dirn.alloc(LM_NDET);
+    SET_SYNC(L.corr_dirn.p, 0, LM_NDET * sizeof(LmCorrDirRecN), st);
   }
   L.err.alloc(16);
   if (c->corr_dir_on) {
@@ -1306,6 +1385,24 @@ CorrDark lane_dark(const lm_ctx* c, Lane& L) {
   return d;
 }
 
+// The lists the ring launches and k_corr_dir read: with the narrow class on,
+// the wide lists in place of k_tile_bound's existing ones (the flags, which
+// k_corr_gen reads, stay).
+CorrDark lane_dark_ring(const lm_ctx* c, Lane& L) {
+  CorrDark d = lane_dark(c, L);
+  if (c->narrow_on) {
+    if (d.tail_cnt) {
+      d.tail_cnt = L.nw_cnt.p + LM_NW_CNT_TTW;
+      d.tail_list = L.ttw_list.p;
+    }
+    if (d.pt_cnt) {
+      d.pt_cnt = L.nw_cnt.p + LM_NW_CNT_PTW;
+      d.pt_list = L.ptw_list.p;
+    }
+  }
+  return d;
+}
+
 // The kernel chain of one batch attempt on lane L (part: 0 the kernels before
 // k_corr, 1 k_corr, 2 the kernels after, -1 all).  Kernel arguments depend
 // only on the key of L.graphs (frame pointers and slots reach the kernels
@@ -1321,7 +1418,7 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
     // block 1: k_carry (a rerun keeps slot 0's staged candidates)
     k_prep<<<do_carry ? 2 : 1, 256, 0, st>>>(L.h_slots.d, L.h_frame_ptr.d, L.h_ctl.d, n + 1, L.slots.p, L.frame_ptr.p,
                                              A.ctl.p, L.npos.p, L.err.p, dK, L.keys.p, L.arena[P.prv].hdr.p, P.last_n,
-                                             A.hdr.p, L.dark_cnt.p, L.tail_cnt.p, L.pt_cnt.p);
+                                             A.hdr.p, L.dark_cnt.p, L.tail_cnt.p, L.pt_cnt.p, L.nw_cnt.p);
     T.begin("k_minmax");
     k_minmax<<<dim3(LM_MM_SPLIT, n + 1 - s_lut0), LM_MM_THREADS, 0, st>>>(L.frame_ptr.p, c->bkg.p, c->npix, s_lut0,
                                                                         L.mm.p);
@@ -1348,11 +1445,15 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
         k_tile_bound_ref<<<dim3((unsigned)nproc, 2), LM_TB_THREADS, c->tb_lds, st>>>(
             dK, L.ext.p, c->ext_slot_bytes, s_proc0, c->tb_const.p, dk.flags, dk.tail_flags, dk.tail_cnt, dk.tail_list,
             dk.pt_flags, dk.pt_cnt, dk.pt_list);
-      else
-        (c->tbw_row_loop ? k_tile_bound<true> : k_tile_bound<false>)
+      else {
+        const LmNarrowOut nwo = c->narrow_on ? LmNarrowOut{L.nw_cnt.p, L.ptw_list.p, L.ttw_list.p, L.nw_list.p}
+                                             : LmNarrowOut{nullptr, nullptr, nullptr, nullptr};
+        (c->narrow_on ? (c->tbw_row_loop ? k_tile_bound<true, true> : k_tile_bound<false, true>)
+                      : (c->tbw_row_loop ? k_tile_bound<true, false> : k_tile_bound<false, false>))
             <<<dim3((unsigned)nproc, (unsigned)(K.tbw_nband[0] + K.tbw_nband[1])), LM_TB_THREADS, c->tbw_lds, st>>>(
                 dK, L.rng.p, c->ext_slot_bytes / LM_INGEST_VEC, s_proc0, nproc, c->tb_const.p, dk.flags, dk.tail_flags,
-                dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list, c->tbs_fallback.p);
+                dk.tail_cnt, dk.tail_list, dk.pt_flags, dk.pt_cnt, dk.pt_list, c->tbs_fallback.p, nwo);
+      }
       T.end();
     }
     // the ring launches' wave directory, from the lists as the correlation will read them
@@ -1360,8 +1461,13 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
     if (c->corr_dir_on && std::find(CP.ring.begin(), CP.ring.end(), (char)1) != CP.ring.end()) {
       std::vector<LmDetGroup> groups;
       for (const auto& grp : CP.groups) groups.push_back(grp.second);
-      HIPCHK(launch_corr_dir(st, dK, groups.data(), CP.ring.data(), (int)groups.size(), nproc, dk, L.corr_dir.p,
-                             L.err.p));
+      HIPCHK(launch_corr_dir(st, dK, groups.data(), CP.ring.data(), (int)groups.size(), nproc, lane_dark_ring(c, L),
+                             L.corr_dir.p, L.err.p));
+      if (c->narrow_on && !CP.ngroups.empty()) {
+        std::vector<LmDetGroup> ng;
+        for (const auto& grp : CP.ngroups) ng.push_back(grp.second);
+        HIPCHK(launch_corr_dir_n(st, ng.data(), (int)ng.size(), nproc, L.nw_cnt.p, L.corr_dirn.p, L.err.p));
+      }
     }
   }
   if (part == 1 || part < 0) {
@@ -1373,9 +1479,15 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
       const void* w = c->setup.corr_precision == LM_CORR_F16 ? (const void*)c->weights16.p : (const void*)c->weights.p;
       HIPCHK(launch_corr(grp.first, CP.ring[gi], dim3(G.tile_end[G.n - 1], nproc), CP.threads[gi], CP.lds[gi], st, dK,
                          G, L.ext.p, c->ext_slot_bytes, w, s_proc0, L.keys.p, L.npos.p, L.tailbin.p,
-                         c->tailbin_slot_bytes, lane_dark(c, L),
+                         c->tailbin_slot_bytes, CP.ring[gi] ? lane_dark_ring(c, L) : lane_dark(c, L),
                          c->corr_dir_on && CP.ring[gi] ? L.corr_dir.p + gi : nullptr));
     }
+    // the narrow items of the ring groups' detectors, after the wide ones (the longer waves first)
+    if (c->narrow_on)
+      for (size_t gi = 0; gi < CP.ngroups.size(); ++gi)
+        HIPCHK(launch_corr_n(CP.ngroups[gi].first, nproc, CP.nlds[gi], st, dK, CP.ngroups[gi].second, L.ext.p,
+                             c->ext_slot_bytes, c->weights.p, L.keys.p, L.npos.p, L.tailbin.p, c->tailbin_slot_bytes,
+                             L.nw_cnt.p, L.nw_list.p, c->corr_dir_on ? L.corr_dirn.p + gi : nullptr));
     T.end();
   }
   if (part == 2 || part < 0) {
@@ -2159,6 +2271,58 @@ LM_API lm_status lm_debug_screen_fallback(lm_ctx* ctx, int64_t* out) {
     unsigned long long h = 0;
     COPY_SYNC(&h, ctx->tbs_fallback.p, sizeof(h), hipMemcpyDeviceToHost, ctx->lanes[0]->stream);
     *out = (int64_t)h;
+  });
+}
+
+LM_API lm_status lm_debug_narrow_work(lm_ctx* ctx, int32_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  for (int k = 0; k < 2 * LM_NDET; ++k) out[k] = -1;
+  if (!ctx->narrow_on) return LM_OK;
+  return read_delivered(ctx, no_check, [&](const Lane& L, auto fetch) {
+    int32_t h[LM_NW_CNT_WORDS];
+    fetch(h, L.nw_cnt.p, sizeof(h));
+    for (int d = 0; d < LM_NDET; ++d) {
+      const LmDet& D = ctx->K.det[d];
+      if (!(D.kind != 0 ? ctx->tailskip_on : ctx->pointskip_on)) continue;  // (not listed by k_tile_bound)
+      const int32_t* w = h + (D.kind != 0 ? LM_NW_CNT_TTW + D.view * LM_TL_NC : LM_NW_CNT_PTW + D.list * LM_TL_NC);
+      out[2 * d] = std::accumulate(h + LM_NW_CNT_N + d * LM_TL_NC, h + LM_NW_CNT_N + (d + 1) * LM_TL_NC, 0);
+      out[2 * d + 1] = std::accumulate(w, w + LM_TL_NC, 0);
+    }
+  });
+}
+
+LM_API lm_status lm_debug_narrow_entries(lm_ctx* ctx, int32_t det, int32_t narrow, uint64_t* out, int32_t cap, int32_t* n) {
+  if (!ctx || !out || !n) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  *n = 0;
+  if (!ctx->narrow_on) return fail(LM_ERR_INVALID_ARGUMENT, "the narrow class is off");
+  if (det < 0 || det >= LM_NDET) return fail(LM_ERR_INVALID_ARGUMENT, "index out of range");
+  const LmConst& K = ctx->K;
+  const LmDet& D = K.det[det];
+  if (!(D.kind != 0 ? ctx->tailskip_on : ctx->pointskip_on)) return LM_OK;
+  return read_delivered(ctx, no_check, [&](const Lane& L, auto fetch) {
+    int32_t h[LM_NW_CNT_WORDS];
+    fetch(h, L.nw_cnt.p, sizeof(h));
+    const bool tail = D.kind != 0;
+    const int v = D.view, ntile = tail ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
+    const int G = (ctx->delivered.slots + LM_INGEST_FB - 1) / LM_INGEST_FB;
+    const int32_t* cnt = h + (narrow ? LM_NW_CNT_N + det * LM_TL_NC
+                                     : tail ? LM_NW_CNT_TTW + v * LM_TL_NC : LM_NW_CNT_PTW + D.list * LM_TL_NC);
+    const int64_t lo = tail ? (int64_t)v * K.tt_stride : (int64_t)D.list * K.tl_stride;
+    int32_t got = 0;
+    for (int c = 0; c < LM_TL_NC; ++c) {
+      const int64_t so = (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile;
+      const int m = std::min(cnt[c], cap - got);
+      if (m <= 0) continue;
+      if (narrow) {
+        fetch(out + got, L.nw_list.p + (tail ? (int64_t)LM_NLIST * K.tl_stride : 0) + lo + so, sizeof(uint64_t) * m);
+      } else {
+        std::vector<uint32_t> w((size_t)m);
+        fetch(w.data(), (tail ? L.ttw_list.p : L.ptw_list.p) + lo + so, sizeof(uint32_t) * m);
+        for (int i = 0; i < m; ++i) out[got + i] = w[i];
+      }
+      got += m;
+    }
+    *n = got;
   });
 }
 

@@ -29,7 +29,7 @@ EXPORTED = (
     "lm_detect_submit", "lm_detect_submit_device", "lm_detect_collect", "lm_ctx_lanes", "lm_ctx_pending",
     "lm_debug_corr_work", "lm_debug_batch_slots", "lm_debug_dark_tile_width",
     "lm_debug_dark_tile_height", "lm_debug_tail_work", "lm_debug_tail_tiles", "lm_debug_point_work",
-    "lm_debug_point_tiles", "lm_debug_screen_fallback",
+    "lm_debug_point_tiles", "lm_debug_screen_fallback", "lm_debug_narrow_work", "lm_debug_narrow_entries",
 )
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -217,6 +217,9 @@ def lib():
         L.lm_debug_point_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.lm_debug_point_tiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
         L.lm_debug_screen_fallback.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.lm_debug_narrow_work.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.lm_debug_narrow_entries.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.POINTER(C.c_int32)]
         L.lm_debug_batch_slots.argtypes = [C.c_void_p]
         L.lm_debug_batch_slots.restype = C.c_int32
         L.lm_synth_frames_device.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
@@ -471,6 +474,26 @@ class Context:
         out = C.c_int64(0)
         _check(lib().lm_debug_screen_fallback(self._h, C.byref(out)))
         return int(out.value)
+
+    def narrow_work(self):
+        """{detector id: (narrow, wide)} tiles of the last batch's ring work
+        (lm_debug_narrow_work); None where the narrow class is off."""
+        out = (C.c_int32 * 12)()
+        _check(lib().lm_debug_narrow_work(self._h, out))
+        if all(out[k] < 0 for k in range(12)):
+            return None
+        return {d: (out[2 * d], out[2 * d + 1]) for d in range(6) if out[2 * d] >= 0}
+
+    def narrow_entries(self, det, narrow, cap=None):
+        """u64 entries of detector det's narrow (or wide) list of the last
+        batch (lm_debug_narrow_entries): slot << 16 | tile in the low word,
+        first block | count << 4 in the high word of a narrow one."""
+        if cap is None:  # the list's own count
+            cap = max(1, (self.narrow_work() or {}).get(det, (0, 0))[0 if narrow else 1])
+        out = np.zeros(cap, np.uint64)
+        n = C.c_int32(0)
+        _check(lib().lm_debug_narrow_entries(self._h, det, 1 if narrow else 0, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def tail_tiles(self, f, view):
         """[tile rows, tile columns] u8: 1 where frame f's tile of tail
