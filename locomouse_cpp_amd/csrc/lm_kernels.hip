@@ -857,13 +857,24 @@ __global__ __launch_bounds__(LM_TB_THREADS) void k_tile_bound_ref(
 //      and there in fp32 first (lm_tbs_*: one packed FMA per term; only a lane
 //      whose fp32 sum lies within its proven margin of zero takes the double
 //      loop, and tbs_fallback counts those lanes; LM_TILE_SCREEN=0 or a
-//      detector the screen's gate refuses: the double loop alone); one
-//      compaction then drops the entries of proven tiles from all three
+//      detector the screen's gate refuses: the double loop alone).  An
+//      unproven block marks its entry.
+//   Without the narrow class (NARROW false):
+//   4c. One compaction drops the entries of proven tiles from all three
 //      segments.
 //   5. One global atomic per (workgroup, detector) on the slot group's segment
 //      counter (the segment index comes from the slot and the batch's slot
 //      count nslot, so all bands of a slot append to one segment), then the
 //      entries are copied out.
+//   With it (NARROW true) nothing follows 4b's barrier but
+//   5w. one wave per detector of the view (the fourth leaves): it reads the
+//      detector's entries and marks where 4b left them, 64 at a time, writes
+//      a refined tile's flag, counts the kept entries per class by ballots,
+//      takes its places in the wide and the narrow list of the slot group's
+//      segment and adds to the listed and bright counters (one lane, the
+//      atomics back to back), then writes each kept entry once, straight from
+//      LDS to its list.  Nothing is closed up and the existing lists (pt_list,
+//      tt_list) are not written: with the class on nothing reads them.
 // No index of a loop is divided at run time (lm_div by reciprocals).
 DEV uint32_t range_merge(uint32_t a, uint32_t b) { return lm_tb_range_merge(a, b); }  // of two words of block ranges
 // The place of each lane with p set in the sequence counted by *ctr (LDS): one
@@ -890,13 +901,15 @@ DEV int wave_append(bool p, int* ctr) {
 // chosen among the three uniform values, not loaded per lane.
 #define TBW_SEL(a) (k == 0 ? a[0] : k == 1 ? a[1] : a[2])
 // NARROW (LM_CORR_NARROW, lm_corr_narrow.h): step 4b marks an entry with the
-// mask of its unproven blocks instead of 0 / 1, the masks close up with the
-// entries, and step 5 also appends every kept entry to one of two further
-// lists of its detector, which the ring kernels then read in place of the
-// existing ones: narrow (the unproven blocks span at most two: the entry with
-// the span's first block and length) or wide (every other, as in the existing
-// list; all of a detector that is not refined or has LmConst::nw_on 0).  The
-// existing flags, lists and counters are written as without it.
+// mask of its unproven blocks instead of 0 / 1, and step 5w appends every kept
+// entry to one of two lists of its detector, which the ring kernels read in
+// place of the existing ones: narrow (the unproven blocks span at most two:
+// the entry with the span's first block and length) or wide (every other, as
+// in the existing list; all of a detector that is not refined or has
+// LmConst::nw_on 0).  The existing flags and counters are written as without
+// it; the existing lists are not written (nwo is set: the host launches NARROW
+// only with the class's lists).  Within a workgroup a detector's entries of
+// one class stand in entry order; every reader takes them in any order.
 template <bool ROWS, bool NARROW>
 __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(LM_TBW_WPE, 8))) void k_tile_bound(
     const LmConst* __restrict__ Kp, const uint32_t* __restrict__ rng, int64_t rng_slot, int s0, int nslot,
@@ -906,12 +919,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
     const LmNarrowOut nwo) {
   const LmConst& K = *Kp;
   extern __shared__ __attribute__((aligned(16))) uint8_t tbw_lds[];
-  __shared__ int s_n[3], s_b[3], s_m[3], s_base[3], s_nw;
-  __shared__ int s_c[3][2], s_g[3][2], s_p[3][2];  // NARROW: entries, list places and entries written per (detector, class)
-  if (NARROW && threadIdx.x < 6) {
-    s_c[threadIdx.x >> 1][threadIdx.x & 1] = 0;
-    s_p[threadIdx.x >> 1][threadIdx.x & 1] = 0;
-  }
+  __shared__ int s_n[3], s_b[3], s_m[3], s_base[3], s_nw;  // (s_m, s_base: NARROW false only)
   const int v = (int)blockIdx.y < K.tbw_nband[0] ? 0 : 1;
   const int band = (int)blockIdx.y - (v ? K.tbw_nband[0] : 0);
   const int slot = s0 + (int)blockIdx.x;
@@ -919,7 +927,7 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   if (tid < 3) {
     s_n[tid] = 0;
     s_b[tid] = 0;
-    s_m[tid] = 0;
+    if (!NARROW) s_m[tid] = 0;
   }
   if (tid == 0) s_nw = 0;
   // the view's detectors (paw, snout, tail: ids 3 v + k) in this band: on =
@@ -1154,7 +1162,8 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
   // block the detector's window ends in, the term reads V (that block alone).  Then row by row (B)
   // at LM_TB_RH 1 (or over the rows of a short last tile row), the pairs formed
   // from B.  A tile with a block that stays unproven is marked and keeps its
-  // entry, the others get flag 0 and the entries of each detector close up.
+  // entry, the others get flag 0 and their entries are dropped (NARROW false:
+  // the entries of each detector close up; NARROW true: step 5w skips them).
   // With ROWS a detector of one chunk per row takes lm_tbr_sum_rows_n, the same
   // terms in the same order with the group count a constant: no chunk counter,
   // no guard per term, a fixed step of nw words to the next row's entries, and
@@ -1311,123 +1320,143 @@ __global__ __launch_bounds__(LM_TB_THREADS) __attribute__((amdgpu_waves_per_eu(L
       }
     }
     __syncthreads();
-    // the marked entries of each detector close up: a group of entries is read
-    // into registers, then written (an entry moves down or stays, and a later
-    // group's entries lie above every place written before, so one barrier per
-    // group of LM_TBW_CR * T entries, which a band's entries rarely exceed)
-    constexpr int CR = LM_TBW_CR;
-    for (int g0 = 0; g0 < nref; g0 += CR * T) {
-      uint32_t en[CR], mk[CR];
-      int kk[CR];
+    // 4c. (NARROW false) the marked entries of each detector close up: a group
+    // of entries is read into registers, then written (an entry moves down or
+    // stays, and a later group's entries lie above every place written before,
+    // so one barrier per group of LM_TBW_CR * T entries, which a band's entries
+    // rarely exceed)
+    if constexpr (!NARROW) {
+      constexpr int CR = LM_TBW_CR;
+      for (int g0 = 0; g0 < nref; g0 += CR * T) {
+        uint32_t en[CR], mk[CR];
+        int kk[CR];
 #pragma unroll
-      for (int u = 0; u < CR; ++u) {
-        const int i = g0 + u * T + tid;
-        const bool act = i < nref;
-        const int k = i < nr3[0] ? 0 : i < nr3[0] + nr3[1] ? 1 : 2;
-        const int t = i - (k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]);
-        en[u] = act ? reinterpret_cast<const uint32_t*>(tbw_lds + TBW_SEL(ent3))[t] : 0u;
-        mk[u] = act ? mark[i] : 0u;
-        const bool kp = mk[u] != 0u;
+        for (int u = 0; u < CR; ++u) {
+          const int i = g0 + u * T + tid;
+          const bool act = i < nref;
+          const int k = i < nr3[0] ? 0 : i < nr3[0] + nr3[1] ? 1 : 2;
+          const int t = i - (k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]);
+          en[u] = act ? reinterpret_cast<const uint32_t*>(tbw_lds + TBW_SEL(ent3))[t] : 0u;
+          mk[u] = act ? mark[i] : 0u;
+          const bool kp = mk[u] != 0u;
 
-        kk[u] = kp ? k : -1;
-        if (act) TBW_SEL(fl)[en[u] & 0xFFFFu] = kp ? 1 : 0;
+          kk[u] = kp ? k : -1;
+          if (act) TBW_SEL(fl)[en[u] & 0xFFFFu] = kp ? 1 : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < CR; ++u)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const bool mine = kk[u] == k;
+            const int pos = wave_append(mine, &s_m[k]);
+            if (mine) reinterpret_cast<uint32_t*>(tbw_lds + ent3[k])[pos] = en[u];
+          }
       }
       __syncthreads();
-#pragma unroll
-      for (int u = 0; u < CR; ++u)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const bool mine = kk[u] == k;
-          const int pos = wave_append(mine, &s_m[k]);
-          if (mine) reinterpret_cast<uint32_t*>(tbw_lds + ent3[k])[pos] = en[u];
-          // (the entry's mask moves with it: down or not at all inside its detector's marks, like the entry)
-          if (NARROW && mine) mark[(k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]) + pos] = mk[u];
-        }
-    }
-    __syncthreads();
-    if (tid < 3) {
-      const int k = tid;
-      if (TBW_SEL(nr3) > 0) s_n[k] = s_m[k];
-    }
-  }
-  __syncthreads();
-  // 5. this workgroup's list segments and their counters, as in k_ingest
-  const int G = (nslot + LM_INGEST_FB - 1) / LM_INGEST_FB;
-  const int c = ((int)blockIdx.x / LM_INGEST_FB) * LM_TL_NC / G;
-  if (tid < 3 && (K.det[3 * v + tid].kind != 0 ? tt_cnt != nullptr : pt_cnt != nullptr)) {
-    const LmDet& D = K.det[3 * v + tid];
-    int32_t* __restrict__ cnt = D.kind != 0 ? tt_cnt + v * LM_TL_NC : pt_cnt + D.list * LM_TL_NC;
-    s_base[tid] = s_n[tid] ? atomicAdd(&cnt[c], s_n[tid]) : 0;
-    if (D.kind == 0 && s_b[tid]) atomicAdd(&pt_cnt[(LM_NLIST + D.list) * LM_TL_NC + c], s_b[tid]);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (!on[k] || s_n[k] == 0) continue;
-    const LmDet& D = K.det[3 * v + k];
-    const int ntile = tail[k] ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
-    const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + K.tbw_ent[3 * v + k]);
-    uint32_t* __restrict__ out =
-        (tail[k] ? tt_list + (int64_t)v * K.tt_stride : pt_list + (int64_t)D.list * K.tl_stride) +
-        (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
-    for (int p = tid; p < s_n[k]; p += T) out[p] = ent[p];
-  }
-  // 5n. the same entries once more, by class (NARROW): counted, one global
-  // atomic per (workgroup, detector, class) on the class's segment counter,
-  // then written
-  if constexpr (NARROW) {
-    if (nwo.cnt == nullptr) return;
-    bool split[3];
-    int mbk[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      split[k] = refine[k] && K.nw_on[3 * v + k] != 0;
-      mbk[k] = k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (!on[k]) continue;
-      const int n = s_n[k];
-      for (int p0 = 0; p0 < n; p0 += T) {
-        const int p = p0 + tid;
-        const bool act = p < n, nar = act && split[k] && lm_nw_classify(mark[mbk[k] + p]).narrow != 0;
-        const unsigned long long mn = __ballot(nar), mw = __ballot(act && !nar);
-        if ((tid & 63) == 0) {
-          if (mn != 0ull) atomicAdd(&s_c[k][1], (int)__popcll(mn));
-          if (mw != 0ull) atomicAdd(&s_c[k][0], (int)__popcll(mw));
-        }
+      if (tid < 3) {
+        const int k = tid;
+        if (TBW_SEL(nr3) > 0) s_n[k] = s_m[k];
       }
     }
+  }
+  // this workgroup's list segment, as in k_ingest
+  const int G = (nslot + LM_INGEST_FB - 1) / LM_INGEST_FB;
+  const int c = ((int)blockIdx.x / LM_INGEST_FB) * LM_TL_NC / G;
+  if constexpr (NARROW) {
+    // 5w. the lists by class, a wave per detector.  The entries and their
+    // marks stand where steps 4 and 4b left them (4b's barrier, or step 4's
+    // when no detector is refined, is the last of the workgroup); a wave
+    // without a detector, with a detector that is not listed or with one that
+    // has neither an entry nor a bright tile leaves by a scalar branch.
+    static_assert(LM_TB_THREADS >= 3 * 64, "a wave per detector of a view");
+    const int k = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    if (k >= 3 || !TBW_SEL(on)) return;
+    const int d = 3 * v + k;
+    const LmDet& D = K.det[d];
+    const bool tl = D.kind != 0;
+    const int n = __builtin_amdgcn_readfirstlane(s_n[k]);
+    const int nb = tl ? 0 : __builtin_amdgcn_readfirstlane(s_b[k]);  // a point detector's bright tiles
+    if (n == 0 && nb == 0) return;
+    const bool rf = TBW_SEL(refine), sp = rf && K.nw_on[d] != 0;
+    const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + TBW_SEL(ent3));
+    const uint32_t* mk = mark + (k == 0 ? 0 : k == 1 ? nr3[0] : nr3[0] + nr3[1]);  // (a refined detector: nr3[k] == n)
+    uint8_t* __restrict__ flk = TBW_SEL(fl);
+    // entries p0 .. p0 + 63 of the detector: lane's entry e, its class cls (0 dropped: a refined tile with every
+    // block proven, 1 wide, 2 narrow) and a narrow one's span fc (first | count << 4)
+    uint32_t e = 0u;
+    int cls = 0, fc = 0;
+    auto chunk = [&](int p0, bool flags) {
+      const int p = p0 + lane;
+      cls = 0;
+      if (p < n) {
+        e = ent[p];
+        const uint32_t m = rf ? mk[p] : 0u;
+        const bool kept = !rf || m != 0u;
+        if (flags && rf) flk[e & 0xFFFFu] = kept ? 1 : 0;
+        const LmNwClass cl = sp ? lm_nw_classify(m) : LmNwClass{0, 0, 0};
+        cls = !kept ? 0 : cl.narrow != 0 ? 2 : 1;
+        fc = cl.first | cl.count << 4;
+      }
+    };
+    // pass A: the flags of a refined detector's tiles and the kept entries per class
+    int cn = 0, cw = 0;
+    for (int p0 = 0; p0 < n; p0 += 64) {
+      chunk(p0, true);
+      cn += (int)__popcll(__ballot(cls == 2));
+      cw += (int)__popcll(__ballot(cls == 1));
+    }
+    // the places in the two lists of segment c and the listed and bright counters: one lane, no wait between them
+    int32_t* __restrict__ cnt = tl ? tt_cnt + v * LM_TL_NC : pt_cnt + D.list * LM_TL_NC;
+    int32_t* __restrict__ wcnt = nwo.cnt + (tl ? LM_NW_CNT_TTW + v * LM_TL_NC : LM_NW_CNT_PTW + D.list * LM_TL_NC);
+    int32_t* __restrict__ ncnt = nwo.cnt + LM_NW_CNT_N + d * LM_TL_NC;
+    int gn = 0, gw = 0;
+    if (lane == 0) {
+      if (cn) gn = atomicAdd(&ncnt[c], cn);
+      if (cw) gw = atomicAdd(&wcnt[c], cw);
+      if (cn + cw) atomicAdd(&cnt[c], cn + cw);
+      if (nb) atomicAdd(&pt_cnt[(LM_NLIST + D.list) * LM_TL_NC + c], nb);
+    }
+    if (cn + cw == 0) return;
+    gn = __builtin_amdgcn_readfirstlane(gn);
+    gw = __builtin_amdgcn_readfirstlane(gw);
+    // pass B: every kept entry to its place (one chunk: it is still in the registers)
+    const int ntile = tl ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
+    const int64_t lo = tl ? (int64_t)v * K.tt_stride : (int64_t)D.list * K.tl_stride;  // the detector's lists
+    const int64_t so = (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile;                 // the segment in them
+    uint32_t* __restrict__ wout = (tl ? nwo.ttw_list : nwo.ptw_list) + lo + so;
+    unsigned long long* __restrict__ nout = nwo.n_list + (tl ? (int64_t)LM_NLIST * K.tl_stride : 0) + lo + so;
+    for (int p0 = 0; p0 < n; p0 += 64) {
+      if (n > 64) chunk(p0, false);
+      const unsigned long long bn = __ballot(cls == 2), bw = __ballot(cls == 1);
+      if (cls == 2)
+        nout[gn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bn >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bn, 0u))] =
+            lm_nw_entry(e, fc & 15, fc >> 4);
+      if (cls == 1)
+        wout[gw + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bw >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bw, 0u))] = e;
+      gn += (int)__popcll(bn);
+      gw += (int)__popcll(bw);
+    }
+  } else {
     __syncthreads();
-    if (tid < 6 && on[tid >> 1]) {
-      const int k = tid >> 1, cls = tid & 1, d = 3 * v + k;
-      const LmDet& D = K.det[d];
-      int32_t* __restrict__ cnt = nwo.cnt + (cls ? LM_NW_CNT_N + d * LM_TL_NC
-                                                 : D.kind != 0 ? LM_NW_CNT_TTW + v * LM_TL_NC : LM_NW_CNT_PTW + D.list * LM_TL_NC);
-      s_g[k][cls] = s_c[k][cls] ? atomicAdd(&cnt[c], s_c[k][cls]) : 0;
+    // 5. the segments' counters and the entries
+    if (tid < 3 && (K.det[3 * v + tid].kind != 0 ? tt_cnt != nullptr : pt_cnt != nullptr)) {
+      const LmDet& D = K.det[3 * v + tid];
+      int32_t* __restrict__ cnt = D.kind != 0 ? tt_cnt + v * LM_TL_NC : pt_cnt + D.list * LM_TL_NC;
+      s_base[tid] = s_n[tid] ? atomicAdd(&cnt[c], s_n[tid]) : 0;
+      if (D.kind == 0 && s_b[tid]) atomicAdd(&pt_cnt[(LM_NLIST + D.list) * LM_TL_NC + c], s_b[tid]);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      if (!on[k]) continue;
-      const int n = s_n[k];
+      if (!on[k] || s_n[k] == 0) continue;
       const LmDet& D = K.det[3 * v + k];
       const int ntile = tail[k] ? K.tt_tx[v] * K.tt_ty[v] : K.fl_tx[v] * K.fl_ty[v];
       const uint32_t* ent = reinterpret_cast<const uint32_t*>(tbw_lds + K.tbw_ent[3 * v + k]);
-      const int64_t lo = tail[k] ? (int64_t)v * K.tt_stride : (int64_t)D.list * K.tl_stride;  // the detector's lists
-      const int64_t so = (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile;                      // the segment in them
-      uint32_t* __restrict__ wout = (tail[k] ? nwo.ttw_list : nwo.ptw_list) + lo + so + s_g[k][0];
-      unsigned long long* __restrict__ nout = nwo.n_list + (tail[k] ? (int64_t)LM_NLIST * K.tl_stride : 0) + lo + so + s_g[k][1];
-      for (int p0 = 0; p0 < n; p0 += T) {
-        const int p = p0 + tid;
-        const bool act = p < n;
-        const LmNwClass cl = act && split[k] ? lm_nw_classify(mark[mbk[k] + p]) : LmNwClass{0, 0, 0};
-        const bool nar = cl.narrow != 0;
-        const int pn = wave_append(nar, &s_p[k][1]);
-        if (nar) nout[pn] = lm_nw_entry(ent[p], cl.first, cl.count);
-        const int pw = wave_append(act && !nar, &s_p[k][0]);
-        if (act && !nar) wout[pw] = ent[p];
-      }
+      uint32_t* __restrict__ out =
+          (tail[k] ? tt_list + (int64_t)v * K.tt_stride : pt_list + (int64_t)D.list * K.tl_stride) +
+          (int64_t)lm_tl_y0(c, G) * LM_INGEST_FB * ntile + s_base[k];
+      for (int p = tid; p < s_n[k]; p += T) out[p] = ent[p];
     }
   }
 }
