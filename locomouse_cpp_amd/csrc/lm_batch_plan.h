@@ -109,6 +109,34 @@ inline void lm_bp_check_lut(const lm_geometry& g, const LmSlot& S) {
                                 "I_PAD's zero padding (not supported).");
 }
 
+// The matched context's rule (locomouse_match.h), lm_bp_check_lut's for the
+// same reason: the histogram counts the bottom crop's pixels of the corrected
+// image, and the table is applied to them in I_PAD.
+inline void lm_bp_check_match(const lm_geometry& g, const LmSlot& S) {
+  const int ux = S.crop_x[0] + g.spre_b_w, uy = S.crop_y[0] + g.spre_b_h;
+  if (ux < g.pad_pre_cols || uy < g.pad_pre_rows || ux + g.bb_bottom_mouse.width > g.pad_pre_cols + g.n_cols ||
+      uy + g.bb_bottom_mouse.height > g.pad_pre_rows + g.n_rows)
+    throw std::invalid_argument("use_reference_image_brightness: frame " + std::to_string(S.frame) +
+                                ": the bottom crop leaves the corrected image, so its histogram would count "
+                                "I_PAD's zero padding and the table would reach it (not supported).");
+}
+
+// A matched context's tables: k_match computes one for every slot with a
+// normalisation table, slots [*s0, *s0 + count) -- the unprocessed slot 0 of a
+// carry too, whose frame is the halo: the table equals what its own batch
+// computed from the same frame, corners and background.
+inline int lm_bp_match_slots(int n, int s_lut0, int* s0) {
+  *s0 = s_lut0;
+  return n + 1 - s_lut0;
+}
+// The slot whose table a reader of slot s's frame uses: the current image
+// (prev = false) carries slot s's, I_PREV_PAD slot s - 1's -- inside that
+// slot's own rectangle.  -1: no such image (the first frame has no I_PREV_PAD).
+inline int lm_bp_match_reader(int s, bool prev, int s_lut0) {
+  const int t = prev ? s - 1 : s;
+  return t >= s_lut0 ? t : -1;
+}
+
 // The slot table of a batch: slots[0 .. n] (frame, active, crops; a slot
 // without a LUT keeps its frame number and is otherwise zero) and the corners
 // of frame first + n - 1 for the next batch.  box: the provided box's corners,
@@ -117,12 +145,13 @@ inline void lm_bp_check_lut(const lm_geometry& g, const LmSlot& S) {
 // of a continuation).  Throws what the reference throws for a crop it cannot
 // take; nothing of the context has changed by then.
 // The ROI rule holds for the processed slots (>= s_proc0).  The LUT rule
+// (and, for a matched context, lm_bp_check_match's in its place)
 // holds for every slot with a LUT (>= s_lut0), the unprocessed slot 0 of a
 // carry too: that one can never newly fail, since the same frame with the
 // same corners passed it as the last slot of its own batch.
 inline void lm_bp_slots(int n, int first, const LmBatchMode& M, const lm_geometry& g, const int (&box)[3],
                         bool gray_lut_on, const int32_t* bb, const int (&last_bb)[3], LmSlot* slots,
-                        int (&new_last_bb)[3]) {
+                        int (&new_last_bb)[3], bool matched = false) {
   std::memcpy(new_last_bb, box, sizeof(box));
   for (int s = 0; s <= n; ++s) {
     LmSlot& S = slots[s];
@@ -137,6 +166,7 @@ inline void lm_bp_slots(int n, int first, const LmBatchMode& M, const lm_geometr
     lm_bp_crop(g, cr, S);
     if (s >= M.s_proc0) lm_bp_check_roi(g, S);
     if (gray_lut_on) lm_bp_check_lut(g, S);
+    if (matched) lm_bp_check_match(g, S);
   }
 }
 

@@ -199,6 +199,14 @@ struct LmConst {
   // bottom crop (LocoMouse_class.cpp:1445-1448)
   int32_t gray_lut_on;
   uint8_t gray_lut[256];
+  // the bottom crop matched to a reference histogram (locomouse_match.h,
+  // lm_match_core.h; never together with gray_lut_on): k_match writes a table
+  // per slot, match_off bytes after the slot's normalisation table (slot s:
+  // luts + 256 s + match_off), from the crop's histogram, match_scale =
+  // (float)(1.0 / (double)(bb_bottom_h bb_bottom_w)) and the reference's CDF
+  int32_t match_on, match_off;
+  float match_scale;
+  float match_ref[256];
 };
 
 // x / d without a division, for x >= 0 and x d < 2^31: lm_div(x, lm_rcp(d))

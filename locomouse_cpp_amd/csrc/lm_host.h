@@ -199,6 +199,7 @@ struct LmTrainView {
   int device, npix;        // npix: bytes of a video frame
   int n_rows, n_cols;      // corrected image
   int use_adj, gray_lut_on;
+  int matched;             // a matched context (locomouse_match.h)
   const void* dK;          // LmConst in device memory
   const uint8_t *bkg, *adj;
   const int32_t* cal;

@@ -34,6 +34,7 @@
 #include "lm_introsort.h"
 
 #include "lm_dev_common.h"
+#include "lm_match_core.h"
 #include "lm_corr_narrow.h"
 #include "lm_tail_bound.h"
 #include "lm_tile_plan.h"
@@ -175,6 +176,10 @@ template <class FP>
 DEV uint8_t ipad_pixel_t(FP __restrict__ F, const uint8_t* __restrict__ bkg, const int32_t* __restrict__ cal,
                          const uint8_t* lut, const LmConst& K, const LmSlot& sl, int R, int C) {
   const uint8_t v = ipad_pixel(F, bkg, cal, lut, K, R, C);
+  // a matched context: the slot's own table (k_match), match_off bytes after its normalisation table -- so `lut`
+  // must point into the lane's global table buffer (luts + 256 slot), never at a copy of the table in LDS or
+  // elsewhere; k_post's motion test and k_match_crop, the callers, pass exactly that
+  if (K.match_on) return in_gray_rect(K, sl, R, C) ? lut[K.match_off + v] : v;
   return K.gray_lut_on && in_gray_rect(K, sl, R, C) ? K.gray_lut[v] : v;
 }
 
@@ -340,6 +345,8 @@ DEV void ingest_run_load(const lm_gu8* F, int lo, uint32_t (&d)[5]) {
 #ifndef LM_INGEST_WPE
 #define LM_INGEST_WPE 5  // amdgpu_waves_per_eu minimum: <= 96 VGPRs, so 5 four-wave groups per CU (one round at C3)
 #endif
+// MATCH: a matched context (k_match): the grey LUT is the slot's own table, the tables of the slot group in LDS
+template <bool MATCH>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_WPE, 8))) void k_ingest(const LmConst* __restrict__ Kp, const uint8_t* const* __restrict__ frame_ptr,
                                                  const uint8_t* __restrict__ bkg, const int32_t* __restrict__ cal,
                                                  const uint8_t* __restrict__ luts, const LmSlot* __restrict__ slots,
@@ -381,7 +388,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
   // costs two load latencies, not four (LUT copy, slots, map, frames one
   // after another).
   __shared__ __attribute__((aligned(16))) uint8_t lut[LM_INGEST_FB][256];
-  __shared__ uint8_t glut[256];
+  __shared__ __attribute__((aligned(MATCH ? 8 : 1))) uint8_t glut[MATCH ? LM_INGEST_FB * 256 : 256];
   __shared__ uint8_t s_fl[LM_INGEST_FB][8 / LM_FH][LM_INGEST_MAXTX];  // bright output tiles of the band, per slot
   __shared__ uint32_t s_ent[LM_INGEST_FB * (8 / LM_FH) * LM_INGEST_MAXTX];
   __shared__ int s_n, s_outs, s_base;
@@ -389,14 +396,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
     const int li = i * 8;
     if (li < nf * 256) *reinterpret_cast<uint2*>(&lut[0][0] + li) = *reinterpret_cast<const uint2*>(luts + (int64_t)sb * 256 + li);
   }
-  for (int i = tid; i < 256; i += T) glut[i] = K.gray_lut[i];
+  if constexpr (MATCH) {
+    for (int i = tid; i < LM_INGEST_FB * 256 / 8; i += T) {
+      const int li = i * 8;
+      if (li < nf * 256) *reinterpret_cast<uint2*>(&glut[0] + li) = *reinterpret_cast<const uint2*>(luts + K.match_off + (int64_t)sb * 256 + li);
+    }
+  } else {
+    for (int i = tid; i < 256; i += T) glut[i] = K.gray_lut[i];
+  }
   for (int i = tid; i < LM_INGEST_FB * FPB * LM_INGEST_MAXTX; i += T) (&s_fl[0][0][0])[i] = 0;
   if (tid == 0) {
     s_n = 0;
     s_outs = 0;
   }
   // the grey LUT's switch and rectangle, read once (in_gray_rect takes them from gk)
-  const bool gray_on = K.gray_lut_on != 0;
+  const bool gray_on = MATCH || K.gray_lut_on != 0;
   GrayRect gk;
   gk.unpad_y[0] = K.unpad_y[0];
   gk.unpad_x[0] = K.unpad_x[0];
@@ -511,7 +525,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
         const uint32_t pk = (pw[k >> 2] >> (8 * (k & 3))) & 0xFFu, bk = (bw[k >> 2] >> (8 * (k & 3))) & 0xFFu;
         uint32_t o = lut[f][pk > bk ? pk - bk : 0];
         // (the grey LUT's rectangle never reaches the pad: the host rejects that)
-        if (GRAY && in_gray_rect(gk, sl, R, C0 + k)) o = glut[o];
+        if (GRAY && in_gray_rect(gk, sl, R, C0 + k)) o = glut[(MATCH ? f * 256 : 0) + o];
         word[k >> 2] |= o << (8 * (k & 3));
       }
 #pragma unroll
@@ -644,6 +658,188 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(LM_INGEST_
     pb[15] = wall_clock64();
   }
 #undef ING_PROF
+}
+
+// ----------------------------------------------------------------- k_match
+// A matched context's table per slot (lm_match_core.h, locomouse_match.h):
+// the histogram of the slot's bottom box I_BOTTOM_MOUSE -- the pixels
+// ipad_pixel returns, before any grey table -- then, on one lane, the CDF and
+// the two loops of the table.  One workgroup of LM_MATCH_THREADS per slot with
+// a normalisation table (the unprocessed slot 0 of a carry too: its frame is
+// the halo, and the table equals what its own batch computed).
+//
+// The box is read in the 16-byte chunks of the bottom ext crop that cover it,
+// as k_ingest reads them: where the lane's source map holds the slot's crop
+// position, a chunk is its map entry, its 16 background bytes and five frame
+// dwords (LM_MATCH_PIPE chunks' loads in flight per lane); elsewhere (a moving
+// box, a gather chunk) the pixels come one by one through ipad_pixel.  The
+// host has checked that the box lies inside I_UNPAD (lm_bp_check_match) and,
+// at creation, inside the bottom ext crop (every point detector's centre tap
+// reads it), so the chunk columns below are non-negative and inside the map.
+//
+// Counts: LM_MATCH_SUB sub-histograms in LDS, bin v of sub-histogram s at
+// [v][s] (lanes that meet on one value spread over LM_MATCH_SUB banks), a lane
+// adds a run of equal bytes of its chunk at once (a crop is mostly the
+// background's 0), and the sub-histograms are summed once at the end.
+#define LM_MATCH_THREADS 256
+#define LM_MATCH_SUB 8
+#define LM_MATCH_PIPE 4
+__global__ __launch_bounds__(LM_MATCH_THREADS) void k_match(const LmConst* __restrict__ Kp,
+                                                            const uint8_t* const* __restrict__ frame_ptr,
+                                                            const uint8_t* __restrict__ bkg,
+                                                            const int32_t* __restrict__ cal, uint8_t* __restrict__ luts,
+                                                            const LmSlot* __restrict__ slots, int s0,
+                                                            const int2* __restrict__ smap, const uint4* __restrict__ sbkg,
+                                                            const int32_t* __restrict__ skey,
+                                                            uint32_t* __restrict__ hist) {
+  const LmConst& K = *Kp;
+  const int slot = s0 + (int)blockIdx.x, tid = (int)threadIdx.x;
+  __shared__ uint32_t s_h[256][LM_MATCH_SUB];
+  __shared__ uint32_t s_cnt[256];
+  __shared__ float s_c[256], s_ref[256];
+  __shared__ uint8_t s_lut[256], s_T[256];
+  const uint8_t* lut = luts + (int64_t)slot * 256;
+  for (int i = tid; i < 256 * LM_MATCH_SUB; i += LM_MATCH_THREADS) (&s_h[0][0])[i] = 0u;
+  for (int i = tid; i < 256; i += LM_MATCH_THREADS) {
+    s_lut[i] = lut[i];
+    s_ref[i] = K.match_ref[i];
+  }
+  const LmSlot sl = slots[slot];
+  const bool mapped = skey[0] == sl.crop_x[0] && skey[1] == sl.crop_y[0];
+  __syncthreads();
+  const lm_gu8* __restrict__ F = as_global(frame_ptr[slot]);
+  // the box in the bottom ext crop: rows ey0 .., byte columns [ex0, ex0 + bw)
+  const int bw = K.bb_bottom_w, bh = K.bb_bottom_h, ew = K.ext_w[0];
+  const int ey0 = K.unpad_y[0] - K.ext_oy[0], ex0 = K.unpad_x[0] - K.ext_ox[0];
+  const int c_lo = ex0 / LM_INGEST_VEC, ncr = (ex0 + bw - 1) / LM_INGEST_VEC - c_lo + 1;  // chunks per row
+  const int nchunk = bh * ncr;
+  uint32_t* const my = &s_h[0][tid & (LM_MATCH_SUB - 1)];
+  // one byte after another, equal neighbours counted together
+  uint32_t run_v = 0u, run_n = 0u;
+  auto count = [&](uint32_t v) {
+    if (v != run_v && run_n) {
+      atomicAdd(my + run_v * LM_MATCH_SUB, run_n);
+      run_n = 0u;
+    }
+    run_v = v;
+    ++run_n;
+  };
+  // chunk i of the box: its ext row and first byte column
+  auto chunk_pos = [&](int i, int& er, int& ec) {
+    const int rr = i / ncr;
+    er = ey0 + rr;
+    ec = (c_lo + i - rr * ncr) * LM_INGEST_VEC;
+  };
+  // the pixels of chunk (er, ec) inside the box, through ipad_pixel
+  auto chunk_gather = [&](int er, int ec) {
+    const int R = sl.crop_y[0] + K.ext_oy[0] + er, C0 = sl.crop_x[0] + K.ext_ox[0] + ec;
+    for (int k = max(0, ex0 - ec); k < min(LM_INGEST_VEC, ex0 + bw - ec); ++k) count(ipad_pixel(F, bkg, cal, s_lut, K, R, C0 + k));
+  };
+  if (mapped) {
+    for (int i0 = tid; i0 < nchunk; i0 += LM_MATCH_PIPE * LM_MATCH_THREADS) {
+      int2 m[LM_MATCH_PIPE];
+      uint4 b4[LM_MATCH_PIPE];
+      uint32_t d[LM_MATCH_PIPE][5];
+#pragma unroll
+      for (int u = 0; u < LM_MATCH_PIPE; ++u) {  // the map entries ...
+        const int i = i0 + u * LM_MATCH_THREADS;
+        m[u] = make_int2(0, 0);
+        b4[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (i < nchunk) {
+          int er, ec;
+          chunk_pos(i, er, ec);
+          const int64_t ci = ((int64_t)er * ew + ec) / LM_INGEST_VEC;
+          m[u] = smap[ci];
+          b4[u] = sbkg[ci];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < LM_MATCH_PIPE; ++u) {  // ... then the frame dwords they point at
+#pragma unroll
+        for (int j = 0; j < 5; ++j) d[u][j] = 0u;
+        if ((m[u].y & 3) != 0) ingest_run_load(F, m[u].x, d[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < LM_MATCH_PIPE; ++u) {
+        const int i = i0 + u * LM_MATCH_THREADS;
+        if (i >= nchunk) continue;
+        int er, ec;
+        chunk_pos(i, er, ec);
+        if ((m[u].y & 3) == 0) {  // a gather chunk
+          chunk_gather(er, ec);
+          continue;
+        }
+        const unsigned sh = (unsigned)(m[u].x & 3);
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_alignbyte(d[u][j + 1], d[u][j], sh);
+        if ((m[u].y & 3) == 2) {  // a flipped run
+          const uint32_t r0 = __builtin_bswap32(w[3]), r1 = __builtin_bswap32(w[2]), r2 = __builtin_bswap32(w[1]),
+                         r3 = __builtin_bswap32(w[0]);
+          w[0] = r0;
+          w[1] = r1;
+          w[2] = r2;
+          w[3] = r3;
+        }
+        const uint32_t bwd[4] = {b4[u].x, b4[u].y, b4[u].z, b4[u].w};
+        const int k0 = ex0 - ec, k1 = ex0 + bw - ec;  // the chunk's bytes [k0, k1) lie in the box
+#pragma unroll
+        for (int k = 0; k < LM_INGEST_VEC; ++k) {
+          const uint32_t pk = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu, bk = (bwd[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+          if (k >= k0 && k < k1) count(s_lut[pk > bk ? pk - bk : 0u]);
+        }
+      }
+    }
+  } else {
+    for (int i = tid; i < nchunk; i += LM_MATCH_THREADS) {
+      int er, ec;
+      chunk_pos(i, er, ec);
+      chunk_gather(er, ec);
+    }
+  }
+  if (run_n) atomicAdd(my + run_v * LM_MATCH_SUB, run_n);
+  __syncthreads();
+  if (tid < 256) {
+    uint32_t n = 0u;
+#pragma unroll
+    for (int s = 0; s < LM_MATCH_SUB; ++s) n += s_h[tid][s];
+    s_cnt[tid] = n;
+    hist[(int64_t)slot * 256 + tid] = n;
+  }
+  __syncthreads();
+  if (tid == 0) {  // serial by definition: a float sum in index order, cur carried across i
+    lm_match_cdf_of(s_cnt, K.match_scale, s_c);
+    lm_match_table(s_c, s_ref, s_T);
+  }
+  __syncthreads();
+  if (tid < 256) luts[(int64_t)slot * 256 + K.match_off + tid] = s_T[tid];
+}
+
+// lm_debug_match_crop (debug bit 1): the bottom box of every frame f of the
+// batch as its steps see it, through ipad_pixel_t: image 2 f the current image
+// (slot f + 1), image 2 f + 1 I_PREV_PAD at the same position (slot f, with
+// its own table inside its own box; zeros where there is no such slot).
+__global__ __launch_bounds__(256) void k_match_crop(const LmConst* __restrict__ Kp,
+                                                    const uint8_t* const* __restrict__ frame_ptr,
+                                                    const uint8_t* __restrict__ bkg, const int32_t* __restrict__ cal,
+                                                    const uint8_t* __restrict__ luts, const LmSlot* __restrict__ slots,
+                                                    int s_lut0, uint8_t* __restrict__ out) {
+  const LmConst& K = *Kp;
+  const int n = K.bb_bottom_w * K.bb_bottom_h;
+  const int scur = (int)blockIdx.y + 1, prev = (int)blockIdx.z, sread = scur - prev;
+  uint8_t* __restrict__ o = out + (int64_t)(2 * (int)blockIdx.y + prev) * n;
+  const LmSlot sc = slots[scur];
+  if (sread < s_lut0) {
+    for (int p = (int)(blockIdx.x * blockDim.x + threadIdx.x); p < n; p += (int)(gridDim.x * blockDim.x)) o[p] = 0;
+    return;
+  }
+  const LmSlot sr = slots[sread];
+  const lm_gu8* __restrict__ F = as_global(frame_ptr[sread]);
+  for (int p = (int)(blockIdx.x * blockDim.x + threadIdx.x); p < n; p += (int)(gridDim.x * blockDim.x)) {
+    const int y = p / K.bb_bottom_w, x = p - y * K.bb_bottom_w;
+    o[p] = ipad_pixel_t(F, bkg, cal, luts + (int64_t)sread * 256, K, sr, sc.crop_y[0] + K.unpad_y[0] + y,
+                        sc.crop_x[0] + K.unpad_x[0] + x);
+  }
 }
 
 // ------------------------------------------------------------ k_tile_bound

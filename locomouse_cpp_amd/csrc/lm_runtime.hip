@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "locomouse_hip.h"
+#include "locomouse_match.h"
 #include "lm_host.h"
 #include "lm_batch_plan.h"
 #include "lm_kernels.hip"
@@ -93,6 +94,8 @@ struct Lane {
   DevBuf<unsigned long long> tailmask;  // TAIL_MASK bitmaps, 64 columns per word
   DevBuf<int32_t> npos, err;
   DevBuf<unsigned> mm;        // k_minmax partial (min, max) pairs per slot
+  DevBuf<uint32_t> mhist;     // a matched context: k_match's histogram per slot (its tables follow the luts)
+  DevBuf<uint8_t> mcrop;      // ... with debug bit 1: k_match_crop's two images per frame
   DevBuf<unsigned> tscratch;  // k_tail run tables beyond its LDS
   DevBuf<uint8_t> tail_ws;    // k_tail<true>: per-slot workspace (tail boxes beyond the LDS)
   DevBuf<float> dbg;
@@ -147,7 +150,7 @@ struct Lane {
   } pend;
   int64_t seq = -1;               // submission number of the batch running on this lane (-1: idle)
   int64_t done_seq = -1;          // submission number of the last batch finished here (its debug data)
-  int batch_n = 0, batch_s0 = 1;  // last finished batch
+  int batch_n = 0, batch_s0 = 1, batch_lut0 = 1;  // last finished batch
   // pipelined halos: the batch's last frame copied to the context's handoff
   // buffer / the predecessor's handoff frame copied into this lane's halo
   hipEvent_t ev_snap = nullptr, ev_consumed = nullptr;
@@ -196,6 +199,9 @@ struct lm_ctx {
   lm_params params{};
   lm_geometry geo{};
   LmConst K{};
+  // a matched context (lm_ctx_create_matched): the reference image's CDF
+  bool matched = false;
+  float match_ref[256] = {0};
   int npix = 0;
   int64_t fstride = 0;                 // device frame pitch of the staging slots
   int bb_x = 0, bb_yb = 0, bb_ys = 0;  // provided-box bottom-right corners
@@ -988,6 +994,16 @@ void validate_and_build(lm_ctx* c, const lm_setup* su, const lm_params* P, const
   fill_flag_grid(K, c->nslots);
   plan_tail_lds(c, g);
   fill_list_and_cost_constants(K, g, P, M);
+  if (c->matched) {
+    K.match_on = 1;
+    K.match_off = 256 * c->nslots;
+    K.match_scale = lm_match_scale((int64_t)K.bb_bottom_h * K.bb_bottom_w);
+    std::memcpy(K.match_ref, c->match_ref, sizeof(K.match_ref));
+    // k_match walks the box in chunks of the bottom ext crop, which holds every I_BOTTOM_MOUSE pixel
+    const int ey0 = K.unpad_y[0] - K.ext_oy[0], ex0 = K.unpad_x[0] - K.ext_ox[0];
+    if (ey0 < 0 || ex0 < 0 || ey0 + K.bb_bottom_h > K.ext_h[0] || ex0 + K.bb_bottom_w > K.ext_w[0])
+      throw std::logic_error("a matched context: the bottom box does not lie inside the bottom ext crop.");
+  }
   slot_sizes(c);
   build_corr_plans(c, su);
   const std::vector<float> wts = pad_weights(K, M, w_off);
@@ -1015,7 +1031,12 @@ void lane_alloc(lm_ctx* c, Lane& L) {
   L.frames.alloc((size_t)fstride * ns);
   L.halo.alloc(fstride);
   SET_SYNC(L.halo.p, 0, fstride, st);
-  L.luts.alloc((size_t)256 * ns);
+  L.luts.alloc((size_t)256 * ns * (c->matched ? 2 : 1));  // a matched context: k_match's tables after them
+  if (c->matched) {
+    L.mhist.alloc((size_t)256 * ns);
+    SET_SYNC(L.luts.p, 0, (size_t)512 * ns, st);
+    SET_SYNC(L.mhist.p, 0, sizeof(uint32_t) * 256 * ns, st);
+  }
   L.mm.alloc((size_t)2 * LM_MM_SPLIT * ns);
   // slack: the last tiles' windows (and the fill's 16-byte rounding) read past
   // the last slot's side view; those pixels only feed outputs that are discarded
@@ -1424,6 +1445,20 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
                                                                         L.mm.p);
     k_lut<<<(n + 1 - s_lut0 + 3) / 4, 256, 0, st>>>(L.mm.p, s_lut0, n + 1, c->adj.p, c->setup.method != 0, L.luts.p);
     T.end();
+    if (c->matched) {  // the bottom crop's histogram and table of every slot with a LUT (lm_bp_match_slots)
+      T.begin("k_match");
+      int ms0 = 0;
+      const int mcount = lm_bp_match_slots(n, s_lut0, &ms0);
+      k_match<<<mcount, LM_MATCH_THREADS, 0, st>>>(dK, L.frame_ptr.p, c->bkg.p, c->cal.p, L.luts.p, L.slots.p, ms0,
+                                                   L.smap.p, L.sbkg.p, L.skey.p, L.mhist.p);
+      T.end();
+      if (c->debug & 1) {  // lm_debug_match_crop: the frames are read now (slot 0's is overwritten when the batch ends)
+        const size_t box = (size_t)K.bb_bottom_w * K.bb_bottom_h;
+        if (!L.mcrop.p) L.mcrop.alloc(2 * box * c->max_batch);
+        k_match_crop<<<dim3(16, n, 2), 256, 0, st>>>(dK, L.frame_ptr.p, c->bkg.p, c->cal.p, L.luts.p, L.slots.p, s_lut0,
+                                                     L.mcrop.p);
+      }
+    }
     // ext crops of both views, and (dark tiles) the bright-tile flags and lists
     T.begin("k_ingest");
     const CorrDark dk = lane_dark(c, L);
@@ -1434,7 +1469,7 @@ void enqueue_chain(lm_ctx* c, Lane& L, Arena& A, const Lane::Pending& P, Timer& 
       HIPCHK(hipMemsetAsync(L.kprof_ing.p, 0, sizeof(long long) * 16 * ing_blocks, st));
       kpi = L.kprof_ing.p;
     }
-    k_ingest<<<dim3((unsigned)(K.ing_nb[0] + K.ing_nb[1]), (unsigned)((nproc + LM_INGEST_FB - 1) / LM_INGEST_FB)),
+    (c->matched ? k_ingest<true> : k_ingest<false>)<<<dim3((unsigned)(K.ing_nb[0] + K.ing_nb[1]), (unsigned)((nproc + LM_INGEST_FB - 1) / LM_INGEST_FB)),
                K.ing_threads, 0, st>>>(dK, L.frame_ptr.p, c->bkg.p, c->cal.p, L.luts.p, L.slots.p, s_proc0, n + 1, L.ext.p,
                                         c->ext_slot_bytes, reinterpret_cast<unsigned*>(L.tailbin.p), L.smap.p, L.sbkg.p,
                                         L.skey.p, dk.flags, dk.cnt, dk.list, L.rng.p, kpi);
@@ -1707,7 +1742,8 @@ void check_batch_args(const lm_ctx* c, const Batch& B) {
 // new_last_bb.  Throws before anything reaches the stream.
 void fill_slots(const lm_ctx* c, Lane& L, const Batch& B, const LmBatchMode& M, int (&new_last_bb)[3]) {
   const int box[3] = {c->bb_x, c->bb_yb, c->bb_ys};
-  lm_bp_slots(B.n, B.first, M, c->geo, box, c->K.gray_lut_on != 0, B.bb, c->last_bb, L.h_slots.p, new_last_bb);
+  lm_bp_slots(B.n, B.first, M, c->geo, box, c->K.gray_lut_on != 0, B.bb, c->last_bb, L.h_slots.p, new_last_bb,
+              c->matched);
   L.h_frame_ptr.p[0] = L.halo.p;
   for (int s = 1; s <= B.n; ++s)
     L.h_frame_ptr.p[s] = B.direct ? B.frames + (int64_t)(s - 1) * B.pitch : L.frames.p + (int64_t)s * c->fstride;
@@ -1962,6 +1998,7 @@ void finish_batch(lm_ctx* c, Lane& L) {
   if (c->debug & 8) compare_pack_copy(L, A, HP, ph);
   L.batch_n = P.n;
   L.batch_s0 = P.s_proc0;
+  L.batch_lut0 = P.s_lut0;
   L.done_seq = L.seq;
   P.on = false;
 }
@@ -2037,14 +2074,17 @@ LM_API int32_t lm_abi_version(void) { return LM_ABI_VERSION; }
 
 LM_API const char* lm_last_error(void) { return g_err.c_str(); }
 
-LM_API lm_status lm_ctx_create(int32_t device, const lm_setup* setup, const lm_params* params, const lm_model* model,
-                               int32_t max_batch, lm_ctx** out) {
-  if (!out) return fail(LM_ERR_INVALID_ARGUMENT, "out is NULL");
-  *out = nullptr;
+// lm_ctx_create, and lm_ctx_create_matched (reference_cdf: checked by the caller)
+static lm_status ctx_create(int32_t device, const lm_setup* setup, const lm_params* params, const lm_model* model,
+                            const float* reference_cdf, int32_t max_batch, lm_ctx** out) {
   if (max_batch <= 0) return fail(LM_ERR_INVALID_ARGUMENT, "max_batch must be > 0");
   if (setup && (setup->pipeline_lanes < 0 || setup->pipeline_lanes > LM_MAX_LANES))
     return fail(LM_ERR_INVALID_ARGUMENT, "pipeline_lanes must be in [0, " + std::to_string(LM_MAX_LANES) + "].");
   lm_ctx* c = new lm_ctx();
+  if (reference_cdf) {
+    c->matched = true;
+    std::memcpy(c->match_ref, reference_cdf, sizeof(c->match_ref));
+  }
   lm_status s = guarded([&] {
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
@@ -2091,6 +2131,40 @@ LM_API lm_status lm_ctx_create(int32_t device, const lm_setup* setup, const lm_p
   g_live_streams[c->device & 63].fetch_add((int)c->lanes.size());
   *out = c;
   return LM_OK;
+}
+
+LM_API lm_status lm_ctx_create(int32_t device, const lm_setup* setup, const lm_params* params, const lm_model* model,
+                               int32_t max_batch, lm_ctx** out) {
+  if (!out) return fail(LM_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  return ctx_create(device, setup, params, model, nullptr, max_batch, out);
+}
+
+// ------------------------------------------------- locomouse_match.h
+
+LM_API lm_status lm_match_cdf(const uint8_t* image, int32_t rows, int32_t cols, int64_t pitch, float* out_cdf) {
+  if (!image || !out_cdf) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  if (rows <= 0 || cols <= 0) return fail(LM_ERR_INVALID_ARGUMENT, "rows and cols must be > 0");
+  if (pitch < cols) return fail(LM_ERR_INVALID_ARGUMENT, "pitch smaller than one row");
+  if ((int64_t)rows * cols > 0x7FFFFFFF) return fail(LM_ERR_INVALID_ARGUMENT, "rows * cols must be < 2^31 (32-bit counts)");
+  uint32_t h[256];
+  lm_match_hist(image, rows, cols, pitch, h);
+  lm_match_cdf_of(h, lm_match_scale((int64_t)rows * cols), out_cdf);
+  return LM_OK;
+}
+
+LM_API lm_status lm_ctx_create_matched(int32_t device, const lm_setup* setup, const lm_params* params,
+                                       const lm_model* model, const float* reference_cdf, int32_t max_batch,
+                                       lm_ctx** out) {
+  if (!out) return fail(LM_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  if (!reference_cdf) return fail(LM_ERR_INVALID_ARGUMENT, "reference_cdf is NULL");
+  if (const char* what = lm_match_cdf_bad(reference_cdf)) return fail(LM_ERR_INVALID_ARGUMENT, what);
+  if (params && (params->use_reference_image_brightness || params->transform_gray_values))
+    return fail(LM_ERR_INVALID_ARGUMENT,
+                "a matched context: params->use_reference_image_brightness and params->transform_gray_values must be 0 "
+                "(the matching is asked for by this call; a fixed table and the matched one exclude each other).");
+  return ctx_create(device, setup, params, model, reference_cdf, max_batch, out);
 }
 
 LM_API void lm_ctx_destroy(lm_ctx* ctx) {
@@ -2244,6 +2318,43 @@ LM_API lm_status lm_debug_scores(lm_ctx* ctx, int32_t f, int32_t det, float* out
   };
   return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
     fetch(out, L.dbg.p + (int64_t)(f + 1) * ctx->dbg_slot_floats + ctx->dbg_off[det], sizeof(float) * rows * cols);
+  });
+}
+
+namespace {
+const char* match_bad(const lm_ctx* ctx, const Lane& L, int32_t f) {
+  if (!ctx->matched) return "not a matched context (lm_ctx_create_matched)";
+  if (f < 0 || f >= L.batch_n) return "index out of range";
+  return nullptr;
+}
+}  // namespace
+
+LM_API lm_status lm_debug_match_hist(lm_ctx* ctx, int32_t f, uint32_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  return read_delivered(ctx, [&](const Lane& L) { return match_bad(ctx, L, f); }, [&](const Lane& L, auto fetch) {
+    fetch(out, L.mhist.p + (int64_t)(f + 1) * 256, 256 * sizeof(uint32_t));
+  });
+}
+
+LM_API lm_status lm_debug_match_table(lm_ctx* ctx, int32_t f, uint8_t* out) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  return read_delivered(ctx, [&](const Lane& L) { return match_bad(ctx, L, f); }, [&](const Lane& L, auto fetch) {
+    fetch(out, L.luts.p + ctx->K.match_off + (int64_t)(f + 1) * 256, 256);
+  });
+}
+
+LM_API lm_status lm_debug_match_crop(lm_ctx* ctx, int32_t f, int32_t prev, uint8_t* out, int32_t rows, int32_t cols) {
+  if (!ctx || !out) return fail(LM_ERR_INVALID_ARGUMENT, "null argument");
+  const auto bad = [&](const Lane& L) -> const char* {
+    if (const char* what = match_bad(ctx, L, f)) return what;
+    if (!(ctx->debug & 1) || !L.mcrop.p) return "debug scores not enabled";
+    if (prev != 0 && prev != 1) return "prev must be 0 or 1";
+    if (rows != ctx->K.bb_bottom_h || cols != ctx->K.bb_bottom_w) return "shape mismatch";
+    if (lm_bp_match_reader(f + 1, prev != 0, L.batch_lut0) < 0) return "the video's first frame has no I_PREV_PAD";
+    return nullptr;
+  };
+  return read_delivered(ctx, bad, [&](const Lane& L, auto fetch) {
+    fetch(out, L.mcrop.p + (int64_t)(2 * f + prev) * rows * cols, (size_t)rows * cols);
   });
 }
 
@@ -2448,6 +2559,7 @@ void lm_ctx_train_view(const lm_ctx* c, LmTrainView* v) {
   v->n_cols = c->K.n_cols;
   v->use_adj = c->setup.method != 0;
   v->gray_lut_on = c->K.gray_lut_on;
+  v->matched = c->matched ? 1 : 0;
   v->dK = c->dK.p;
   v->bkg = c->bkg.p;
   v->adj = c->adj.p;

@@ -613,6 +613,9 @@ lm_status gather(lm_train_ctx* c, lm_ctx* det, const uint8_t* frames, int64_t pi
     if (V.device != c->device) throw std::invalid_argument("the detection context is on another device");
     if (V.gray_lut_on)
       throw std::invalid_argument("transform_gray_values: that table moves with the per-frame crop; not gathered");
+    if (V.matched)
+      throw std::invalid_argument("a matched context (lm_ctx_create_matched): the table is the frame's own and moves with "
+                                  "the per-frame crop; not gathered");
     if (n_frames <= 0 || n_frames > 65535) throw std::invalid_argument("n_frames must be in 1..65535");
     if (pitch < V.npix) throw std::invalid_argument("pitch is smaller than a frame");
     check_add(c, n_points);

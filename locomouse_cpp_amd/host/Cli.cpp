@@ -99,7 +99,18 @@ int run(int argc, char** argv) {
   LocoMouse_Inputs li;
   const int method = std::stoi(in.METHOD);  // LocoMouse::initializePaths
   DebugConfig dbg;
-  load_config(in.CONFIG_FILE, in.REF_PATH, li.params, li.bb_params, dbg);
+  // LM_REFERENCE_BRIGHTNESS=intended (not in the reference): use_reference_image_brightness as the reference
+  // means it (LocoMouse_Inputs::reference_intended); unset or empty: as it executes it, which cannot start
+  if (const char* rb = std::getenv("LM_REFERENCE_BRIGHTNESS")) {
+    const std::string v = rb;
+    if (v == "intended") li.reference_intended = true;
+    else if (!v.empty()) throw std::invalid_argument("LM_REFERENCE_BRIGHTNESS: must be intended, not " + v + ".");
+  }
+  ReferenceImage ref_image;
+  load_config(in.CONFIG_FILE, in.REF_PATH, li.params, li.bb_params, dbg, &ref_image);
+  li.reference_rows = ref_image.rows;
+  li.reference_cols = ref_image.cols;
+  li.reference_image = std::move(ref_image.px);
   auto video = std::make_shared<AviReader>();
   if (!video->open(in.VIDEO_FILE)) throw std::invalid_argument("Could not open the video file: " + in.VIDEO_FILE + ".");
   li.n_frames = video->frame_count();
@@ -232,7 +243,14 @@ int run(int argc, char** argv) {
     }
     unsigned long long bsum = 0;
     for (uint8_t v : bkg) bsum += v;
-    std::cout << "\nbackground_sum " << bsum << std::endl;
+    std::cout << "\nbackground_sum " << bsum;
+    if (P.use_reference_image_brightness) {  // the reference image as the inputs carry it, and whether it will be used
+      unsigned long long rsum = 0;
+      for (uint8_t v : li.reference_image) rsum += v;
+      std::cout << "\nreference " << (li.reference_intended ? "intended " : "as_executed ") << li.reference_rows << " "
+                << li.reference_cols << " " << rsum;
+    }
+    std::cout << std::endl;
     return EXIT_SUCCESS;
   }
   {  // OUTPUT = FileStorage(output_file, WRITE) must open (:333-337)

@@ -48,7 +48,8 @@ void LocoMouse::debug_frames(int first, int n) {
       << "I_PAD.size(): [" << g.ipad_cols << " x " << g.ipad_rows << "]" << std::endl
       << "BB_BOTTOM_MOUSE_PAD: " << debug_rect(lm_rect{bx, by, bp.width, bp.height}) << std::endl
       << "BB_UNPAD_MOUSE_BOTTOM: " << debug_rect(g.bb_unpad_mouse_bottom) << std::endl;
-    if (IN.params.transform_gray_values) T << "Gray Level Transformation Done" << std::endl;
+    if (IN.reference_intended && IN.params.use_reference_image_brightness) T << "Histogram matching done" << std::endl;  // :1441-1443
+    else if (IN.params.transform_gray_values) T << "Gray Level Transformation Done" << std::endl;
     T << "BB_SIDE_MOUSE_PAD: " << debug_rect(lm_rect{bx, sy, sp.width, sp.height}) << std::endl
       << "BB_UNPAD_MOUSE_SIDE: " << debug_rect(g.bb_unpad_mouse_side) << std::endl;
     if (f > 0) T << "Cropped previous frame. " << std::endl;

@@ -27,7 +27,7 @@ void Model::rebind() {
 // LocoMouse_Parameters (LocoMouse_class.cpp:4-249): keys in the reference's
 // order, its messages, OpenCV's missing-key-reads-0 semantics.
 void load_config(const std::string& file, const std::string& ref_path, lm_params& P, lm_bb_params& B,
-                 DebugConfig& D) {
+                 DebugConfig& D, ReferenceImage* ref) {
   FsNode c;
   if (!read_file_storage(file, c)) throw std::invalid_argument("Failed to read config file: " + file + ".");
   const std::string E = "Invalid configuration parameter: ";
@@ -102,6 +102,10 @@ void load_config(const std::string& file, const std::string& ref_path, lm_params
       } else {
         bad("Failed to open reference image: " + name + ".");
       }
+    } else if (ref) {
+      ref->rows = r;
+      ref->cols = cc;
+      ref->px = std::move(px);
     }
   }
   if (P.transform_gray_values & ~(int)both) {

@@ -21,9 +21,19 @@ struct DebugConfig {
   int n_frames = 0;      // LM_N_FRAMES_TO_DEBUG (N_debug_frames, :21-26)
 };
 
+// config.yml's reference image (use_reference_image_brightness, :160-189), as
+// read_png_gray hands it: a colour file is converted to grey, where the
+// reference's imread would have handed computeNormalizedCDF channel 0.
+struct ReferenceImage {
+  int rows = 0, cols = 0;
+  std::vector<uint8_t> px;  // rows x cols; empty: none was read
+};
+
 // Keys in the reference's order, its messages, OpenCV's missing-key-reads-0
-// semantics.  Throws std::invalid_argument.
-void load_config(const std::string& file, const std::string& ref_path, lm_params& P, lm_bb_params& B, DebugConfig& D);
+// semantics.  Throws std::invalid_argument.  ref: where the reference image's
+// pixels go when use_reference_image_brightness opened it (null: dropped).
+void load_config(const std::string& file, const std::string& ref_path, lm_params& P, lm_bb_params& B, DebugConfig& D,
+                 ReferenceImage* ref = nullptr);
 
 // The six detectors in the file's order: paw_side, paw_bottom, tail_side,
 // tail_bottom, snout_side, snout_bottom.  m's weight pointers point into w:

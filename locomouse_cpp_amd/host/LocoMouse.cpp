@@ -5,6 +5,7 @@
 
 #include "Jpeg.hpp"
 #include "locomouse_jpeg.h"
+#include "locomouse_match.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -143,6 +144,23 @@ void throw_on_error(lm_status s) {
   throw std::runtime_error(lm_last_error());
 }
 
+// The detection context of one device: lm_ctx_create, or, with the reference
+// image's CDF (LocoMouse_Inputs::reference_intended), a matched one.  A matched
+// context takes both grey-level options as 0: with both set in config.yml and
+// the image opened, the reference too uses the image and not the table
+// (:152-192).
+static void create_context(int device, const lm_setup& setup, const lm_params& params, const lm_model& model,
+                           const float* reference_cdf, int batch, lm_ctx** out) {
+  if (!reference_cdf) {
+    throw_on_error(lm_ctx_create(device, &setup, &params, &model, batch, out));
+    return;
+  }
+  lm_params p = params;
+  p.use_reference_image_brightness = 0;
+  p.transform_gray_values = 0;
+  throw_on_error(lm_ctx_create_matched(device, &setup, &p, &model, reference_cdf, batch, out));
+}
+
 // ------------------------------------------------ device decode (MJPEG)
 //
 // One lm_jpeg_ctx and a ring of device frame buffers: a batch of compressed
@@ -252,13 +270,13 @@ struct LocoMouse::DevicePool {
   size_t next = 0;                                                  // the next batch's worker
 
   DevicePool(const std::vector<int>& devices, const lm_setup& setup, const lm_params& params, const lm_model& model,
-             int batch_, size_t frame_bytes_, bool device_decode)
+             const float* reference_cdf, int batch_, size_t frame_bytes_, bool device_decode)
       : frame_bytes(frame_bytes_), batch(batch_), lanes(std::max(1, setup.pipeline_lanes)) {
     try {
       for (int d : devices) {
         auto w = std::make_unique<Worker>();
         w->device = d;
-        throw_on_error(lm_ctx_create(d, &setup, &params, &model, batch, &w->ctx));
+        create_context(d, setup, params, model, reference_cdf, batch, &w->ctx);
         if (device_decode)  // a halo frame travels with its batch: batch + 1 frames per buffer
           w->jpeg = std::make_unique<DeviceJpeg>(d, setup.video_rows, setup.video_cols, batch + 1, 2 * lanes + 1);
         workers.push_back(std::move(w));
@@ -521,13 +539,23 @@ void LocoMouse::initializeFeatureLoop() {
                << "BB_SIDE_MOUSE: " << debug_rect(BB_SIDE_MOUSE) << std::endl
                << "BB_BOTTOM_MOUSE: " << debug_rect(BB_BOTTOM_MOUSE) << std::endl;
   IN.setup.pipeline_lanes = std::max(1, std::min(IN.lanes, LM_MAX_LANES));
+  // use_reference_image_brightness as intended: the reference image's CDF, for a matched context on every device
+  float cdf_buf[256];
+  const float* cdf = nullptr;
+  if (IN.reference_intended && IN.params.use_reference_image_brightness) {
+    if (IN.reference_image.empty() ||
+        IN.reference_image.size() != (size_t)IN.reference_rows * (size_t)IN.reference_cols)
+      throw std::invalid_argument("use_reference_image_brightness: the reference image's pixels are missing.");
+    throw_on_error(lm_match_cdf(IN.reference_image.data(), IN.reference_rows, IN.reference_cols, IN.reference_cols, cdf_buf));
+    cdf = cdf_buf;
+  }
   if (IN.devices.size() > 1) {
-    POOL = std::make_unique<DevicePool>(IN.devices, IN.setup, IN.params, IN.model, IN.batch, FRAME_BYTES,
+    POOL = std::make_unique<DevicePool>(IN.devices, IN.setup, IN.params, IN.model, cdf, IN.batch, FRAME_BYTES,
                                         IN.decode == LocoMouse_Inputs::Decode::device);
     CTX = POOL->first_ctx();
     PENDING.p = POOL->take_buffer();  // pool-owned: handed to the workers and swapped at every flush
   } else {
-    throw_on_error(lm_ctx_create(IN.device, &IN.setup, &IN.params, &IN.model, IN.batch, &CTX));
+    create_context(IN.device, IN.setup, IN.params, IN.model, cdf, IN.batch, &CTX);
     if (IN.decode == LocoMouse_Inputs::Decode::device)
       JPEG = std::make_unique<DeviceJpeg>(IN.device, IN.setup.video_rows, IN.setup.video_cols, IN.batch,
                                           2 * lm_ctx_lanes(CTX) + 1);

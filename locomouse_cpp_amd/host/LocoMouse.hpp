@@ -89,6 +89,15 @@ struct LocoMouse_Inputs {
   // is refused unless `oversubscribe` (rehearsals on fewer GPUs).
   std::vector<int> devices;
   bool oversubscribe = false;
+  // use_reference_image_brightness as intended (include/locomouse_match.h; not
+  // what the reference executes: it cannot start with that option, and
+  // without reference_intended neither does this program).  With it and
+  // params.use_reference_image_brightness, every device's context is a
+  // matched one: lm_match_cdf of the reference image's pixels (config.yml's
+  // reference_image_path, rows x cols) goes to lm_ctx_create_matched.
+  bool reference_intended = false;
+  std::vector<uint8_t> reference_image;
+  int reference_rows = 0, reference_cols = 0;
   // Whole-video BB pass (use_provided_bounding_box = 0): config.yml's
   // median_filter_size / min_pixel_visible / moving_average_window /
   // conn_comp_connectivity, and V.set(CV_CAP_PROP_POS_FRAMES, 0) (:761-762)

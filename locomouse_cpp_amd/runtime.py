@@ -74,6 +74,10 @@ CALIB_EXPORTED = ("lm_calib_default_opts", "lm_calib_create", "lm_calib_destroy"
                   "lm_calib_fit", "lm_calib_map")
 CALIB_CLI_PATH = os.path.join(PKG, "bin", "LocoMouseCalibrate")
 
+# include/locomouse_match.h (the bottom crop matched to a reference image's histogram), same library
+MATCH_EXPORTED = ("lm_match_cdf", "lm_ctx_create_matched", "lm_debug_match_hist", "lm_debug_match_table",
+                  "lm_debug_match_crop")
+
 
 def _up_to_date(obj, cmd):
     """True when obj was built by the same command and is newer than every
@@ -306,6 +310,12 @@ def lib():
         L.lm_calib_fit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(lm_calib_opts),
                                    C.c_int32, C.c_double, C.POINTER(lm_calib_fit_result)]
         L.lm_calib_map.argtypes = [C.POINTER(lm_calib_fit_result), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.lm_match_cdf.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]
+        L.lm_ctx_create_matched.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.POINTER(C.c_void_p)]
+        L.lm_debug_match_hist.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.lm_debug_match_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.lm_debug_match_crop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
         _lib = L
     return _lib
 
@@ -326,11 +336,26 @@ def synth_frames_device(d_ptr, rows, cols, first, n, pitch, device=0):
     _check(lib().lm_synth_frames_device(device, C.c_void_p(d_ptr), rows, cols, first, n, pitch))
 
 
+def match_cdf(image):
+    """The cumulative histogram [256] float32 of a u8 image [rows, cols]
+    (lm_match_cdf, include/locomouse_match.h; host only)."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 2:
+        raise ValueError("image must be a 2-D uint8 array")
+    image = np.ascontiguousarray(image)
+    out = np.zeros(256, np.float32)
+    _check(lib().lm_match_cdf(image.ctypes.data, image.shape[0], image.shape[1], image.shape[1], out.ctypes.data))
+    return out
+
+
 class Context:
     """One lm_ctx on one HIP device (the per-frame loop's state)."""
 
-    def __init__(self, cfg, max_batch=64, device=0, lanes=None):
-        """lanes: pipeline lanes (lm_setup.pipeline_lanes; None keeps cfg.setup's)."""
+    def __init__(self, cfg, max_batch=64, device=0, lanes=None, reference_cdf=None):
+        """lanes: pipeline lanes (lm_setup.pipeline_lanes; None keeps cfg.setup's).
+        reference_cdf: [256] float32 (match_cdf of a reference image): a matched
+        context, every frame's bottom crop matched to that histogram
+        (lm_ctx_create_matched)."""
         self.cfg = cfg  # keeps the arrays behind the structs alive
         self._h = C.c_void_p()
         setup = cfg.setup
@@ -338,8 +363,15 @@ class Context:
             setup = type(cfg.setup).from_buffer_copy(cfg.setup)
             setup.pipeline_lanes = lanes
         self._setup = setup
-        _check(lib().lm_ctx_create(device, C.byref(setup), C.byref(cfg.params), C.byref(cfg.model), max_batch,
-                                   C.byref(self._h)))
+        if reference_cdf is not None:
+            ref = np.ascontiguousarray(reference_cdf, dtype=np.float32)
+            if ref.shape != (256,):
+                raise ValueError("reference_cdf must hold 256 floats")
+            _check(lib().lm_ctx_create_matched(device, C.byref(setup), C.byref(cfg.params), C.byref(cfg.model),
+                                               ref.ctypes.data, max_batch, C.byref(self._h)))
+        else:
+            _check(lib().lm_ctx_create(device, C.byref(setup), C.byref(cfg.params), C.byref(cfg.model), max_batch,
+                                       C.byref(self._h)))
         self.max_batch = max_batch
 
     def lanes(self):
@@ -436,6 +468,26 @@ class Context:
         g = self.geometry()
         out = np.zeros((g.bb_bottom_mouse.height, g.tail_box_width), dtype=np.uint8)
         _check(lib().lm_debug_tail_mask(self._h, f, out.ctypes.data, out.shape[0], out.shape[1]))
+        return out
+
+    def match_hist(self, f):
+        """[256] uint32: the histogram of frame f's bottom crop in the last batch (lm_debug_match_hist)."""
+        out = np.zeros(256, np.uint32)
+        _check(lib().lm_debug_match_hist(self._h, f, out.ctypes.data))
+        return out
+
+    def match_table(self, f):
+        """[256] uint8: frame f's table in the last batch (lm_debug_match_table)."""
+        out = np.zeros(256, np.uint8)
+        _check(lib().lm_debug_match_table(self._h, f, out.ctypes.data))
+        return out
+
+    def match_crop(self, f, prev=False):
+        """The bottom box as frame f's steps see it: the current image, or
+        (prev) I_PREV_PAD at the current box (lm_debug_match_crop; debug bit 1)."""
+        g = self.geometry()
+        out = np.zeros((g.bb_bottom_mouse.height, g.bb_bottom_mouse.width), np.uint8)
+        _check(lib().lm_debug_match_crop(self._h, f, 1 if prev else 0, out.ctypes.data, out.shape[0], out.shape[1]))
         return out
 
     def kernel_times(self):
